@@ -42,6 +42,9 @@ One JSON line is printed by rank 0.  Besides the contract's keys it carries
   widened       -- (1 GPU) the SURVEY 8f rows: fused conditional flow, AR log_prob, the LFI step as a HIP graph,
                    sampling with fresh batch statistics under autograd.
 --no-extras skips train_step, configs and widened (a clean per-kernel average under rocprofv3 --stats).
+--dump-outputs DIR writes the log_prob of the last timed step to DIR/log_prob.npy (rank 0; float32, 4 MB).  The inputs
+(z, parameters, BatchNorm statistics) are seeded and computed without the kernels under test, so the files of two builds
+can be compared element for element.
 """
 import argparse
 import gc
@@ -80,7 +83,14 @@ def parse_args():
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = os.cpu_count()")
     ap.add_argument("--dry-run-launcher", action="store_true",
                     help="print the command the self-launcher would run for --gpus N and exit (no GPU, no children)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: log_prob, float32, "
+                         "(1, 2^20)) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for "
+                         "output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -101,6 +111,8 @@ def launcher_command(args, port=None):
         cmd.append("--no-extras")
     if args.cpu_threads:
         cmd += ["--cpu-threads", str(args.cpu_threads)]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return cmd
 
 
@@ -236,12 +248,24 @@ def main():
 
     def build_model(D_):
         """NormFlow(D, False, 'coupling', 4, 2, 15) with xavier_normal_ params (seed 0) and BatchNorm
-        statistics populated by one 4,096-sample batch-mode forward."""
+        statistics populated by one 4,096-sample batch-mode forward of the host draw
+        that np.random.seed(0) gives.  That forward runs through the CPU oracle on one thread, so the inputs of
+        the timed path are the same from run to run and from build to build (on the GPU the statistics would
+        come from the kernels under test, summed with float64 atomics)."""
         torch.manual_seed(0)
         np.random.seed(0)
         nf_ = tnf.NormFlow(D_, False, "coupling", S, L, U, device=dev)
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        import flow_oracle as orc
+
+        omega = np.random.normal(0.0, 1.0, (1, 4096, D_))
+        threads = torch.get_num_threads()
+        torch.set_num_threads(1)
         with torch.no_grad():
-            nf_(4096)  # batch-statistics forward on the GPU; caches mean/alpha in every BatchNorm
+            _, _, stats = orc.flow_forward(omega, nf_.params.detach().cpu(), D_, S, L, U)
+        torch.set_num_threads(threads)
+        for b, (m, a) in zip(nf_._bn_layers(), stats):
+            b.set_last_stats(m.to(dev), a.to(dev))
         return nf_
 
     nf = build_model(D)
@@ -316,6 +340,10 @@ def main():
     # ... and the measurement proper: the same W + K steps once the clock has settled
     wall, ev, lp = run(nf, z, main_fusion, args.steps, args.warmup)
     wall_max = max_over_ranks(wall)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path received from its last step: log_prob (1, 2^20) float32, 4 MB
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "log_prob.npy"), lp.detach().float().cpu().numpy())
 
     # the per-layer chain (k = 8), outside the timed region
     wall_l, ev_l, lp_l = run(nf, z, L_.FUSE_LAYER, max(5, args.steps // 2), 2)

@@ -8,7 +8,7 @@ against (and to time on the host cores).  Nothing in `torch_nf_amd/` may import
 it: the product path is the HIP extension and fails loudly without it.
 
 Pinned: every function here is checked against outputs of the reference itself
-(imported from /root/reference in the build container by
+(imported from a checkout of the reference in the build container by
 `oracle/gen_golden.py`; vectors committed under `tests/golden/`), to exact
 equality in fp32 and fp64 -- it issues the same aten ops in the same order.
 

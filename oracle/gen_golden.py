@@ -3,11 +3,11 @@
 Usage (cwd must be outside the repo so nothing shadows the reference's
 namespace package):
 
-    cd /tmp && PYTHONDONTWRITEBYTECODE=1 PYTHONPATH=/root/reference \
-        python3 /root/repo/oracle/gen_golden.py
+    cd /tmp && PYTHONDONTWRITEBYTECODE=1 PYTHONPATH=<checkout of the reference> \
+        python3 <this repo>/oracle/gen_golden.py
 
 Every fixture holds the inputs AND the reference's outputs, so the GPU box
-(which never sees /root/reference) needs nothing but the .npz files.  While
+(which never sees the reference) needs nothing but the .npz files.  While
 generating, each case is also replayed through oracle/flow_oracle.py and must
 match the reference exactly (same aten ops, same order) -- that is what pins
 the oracle.  The reference is only imported and called here; no source text
@@ -20,7 +20,7 @@ import sys
 import numpy as np
 import torch
 
-import torch_nf.bijectors as rb  # the reference (PYTHONPATH=/root/reference)
+import torch_nf.bijectors as rb  # the reference (PYTHONPATH=<checkout of the reference>)
 import torch_nf.density_estimator as rde
 from torch_nf.conditional_density_estimator import ConditionalDensityEstimator as RefCDE
 
@@ -30,7 +30,8 @@ spec = importlib.util.spec_from_file_location("flow_oracle", os.path.join(HERE, 
 orc = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(orc)
 
-assert "/root/reference" in rb.__file__, rb.__file__
+# the reference itself, not this package aliased as torch_nf (torch_nf_amd.install_as_torch_nf)
+assert not os.path.abspath(rb.__file__).startswith(os.path.dirname(HERE) + os.sep), rb.__file__
 torch.set_num_threads(1)  # deterministic reduction order for the fixtures
 
 

@@ -4,7 +4,7 @@
 # usage: tools/pmc.sh <outdir under gpurun_out/> [script args]
 #   PMC_SCRIPT=tools/xyz.py  the program to profile (default tools/kbench.py: whole-flow kernel + per-layer chain)
 set -e
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)  # the repository this script lives in
 OUT=$R/gpurun_out/$1; shift
 SCRIPT=${PMC_SCRIPT:-tools/kbench.py}
 case "$SCRIPT" in /*) ;; *) SCRIPT=$R/$SCRIPT ;; esac

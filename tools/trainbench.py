@@ -1,5 +1,5 @@
-import sys, time, torch, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, time, torch, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch_nf_amd as tnf
 D, S, L, U, N = 64, 4, 2, 15, 1 << 19
 torch.manual_seed(0); np.random.seed(0)
