@@ -81,9 +81,12 @@ int tnf_set_option(int32_t key, int32_t value);
  * forward ran and re-enters them where the backward runs. */
 int tnf_get_option(int32_t key, int32_t* value);
 
-/* Diagnostics: how many launches of a backward-kernel family this PROCESS has enqueued so far (any thread, any
- * stream).  Tests that select a kernel through an option read the counters around a step to prove the intended kernel
- * ran (a backward runs on autograd's thread, where a thread-local option set elsewhere would be silently absent). */
+/* Diagnostics: how many launches of a kernel family this PROCESS has enqueued so far (any thread, any stream).  Tests
+ * that select a kernel through an option or a shape read the counters around a call to prove the intended kernel ran (a
+ * backward runs on autograd's thread, where a thread-local option set elsewhere would be silently absent; a forward call
+ * may move to another kernel where the first one's operands no longer fit the LDS).  Families 0-6: backward kernels.
+ * Families 7-15: forward kernels, one count per launch of the kernel named; the small preparation launches of the
+ * flow_range2 chains (operand images, fold constants) and of cond_flow (operand image) are not counted. */
 enum {
     TNF_DIAG_BWD_LAYER_FP32 = 0,  /* coupling_bwd_mfma_kernel: fp32-MFMA layer backward */
     TNF_DIAG_BWD_LAYER_F16 = 1,   /* coupling_bwd_f16_kernel: split-f16 layer backward */
@@ -92,7 +95,17 @@ enum {
     TNF_DIAG_MAF_BWD_MFMA = 4,    /* maf_bwd_mfma_kernel */
     TNF_DIAG_MAF_BWD_GENERIC = 5, /* maf_backward_kernel<T> */
     TNF_DIAG_BWD_WIDE = 6,        /* coupling_wide_bwd_kernel: MFMA backward of the wide coupling shapes */
-    TNF_DIAG_FAMILIES = 8
+    TNF_DIAG_FLOW_FUSED2 = 7,     /* flow_fused2_kernel, inverse (log_prob) direction: the default whole-flow kernel */
+    TNF_DIAG_FLOW_FUSED2_FWD = 8, /* flow_fused2_kernel, sampling direction */
+    TNF_DIAG_FLOW_FUSED3 = 9,     /* flow_fused3_kernel (flow variant 20), inverse direction */
+    TNF_DIAG_FLOW_F16 = 10,       /* flow_fused_f16_kernel: run-time stage loop, both directions */
+    TNF_DIAG_FLOW_FP32 = 11,      /* flow_fused_kernel: fp32-MFMA whole-flow kernel (flow variant 0), both directions */
+    TNF_DIAG_FLOW_RANGE2 = 12,    /* flow_range2_kernel, inverse direction: one count per range of the per-layer chain */
+    TNF_DIAG_FLOW_RANGE2_FWD = 13, /* flow_range2_kernel, sampling direction: one count per layer of the chain */
+    TNF_DIAG_COUPLING_MFMA = 14,  /* coupling_mfma_kernel: fp32-MFMA layer kernel (layer variant 0 chains, training
+                                   * forward of the per-layer pair, bijector-level calls) */
+    TNF_DIAG_COND_FLOW = 15,      /* cond_flow_kernel: conditional flow log_prob, training forward and sampling */
+    TNF_DIAG_FAMILIES = 16
 };
 int64_t tnf_diag_launch_count(int32_t family);
 
@@ -383,6 +396,12 @@ int64_t tnf_flow_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t num_st
 /* Returns 1 if the whole-flow kernel (TNF_FUSE_FLOW) exists for this configuration
  * (MFMA fast path and all 2*S layers' operands fit the 160 KB of LDS), else 0. */
 int tnf_flow_fused_supported(int32_t D, int32_t num_stages, int32_t num_layers, int32_t num_units);
+/* Returns 1 if the default whole-flow kernel (flow_fused2, flow variant 10) / its 32-sample-group form (flow_fused3,
+ * flow variant 20) holds this configuration, else 0.  Within tnf_flow_fused_supported but outside these, the whole-flow
+ * entry points run flow_fused_f16 (its run-time stage loop) instead, and tnf_flow_forward_logq_f32 returns
+ * TNF_EUNSUPPORTED. */
+int tnf_flow_fused2_supported(int32_t D, int32_t num_stages, int32_t num_layers, int32_t num_units);
+int tnf_flow_fused3_supported(int32_t D, int32_t num_stages, int32_t num_layers, int32_t num_units);
 
 /* NormFlow.log_prob (density_estimator.py:408-416) = inverse_and_log_det
  * (density_estimator.py:390-406) + base Gaussian.  Outputs, each optional (NULL):

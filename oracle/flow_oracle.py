@@ -229,8 +229,9 @@ def base_log_density_f64(omega):
 def flow_forward(omega, params, D, num_stages, num_layers, num_units, bn_stats=None):
     """density_estimator.py:364-388 with the host draw `omega` (float64 numpy,
     shape (M,N,D)) injected.  bn_stats=None -> batch statistics (freeze_bn=False),
-    else the frozen (mean, alpha) pairs.  Returns (z fp32, log_q fp64, bn_stats)."""
-    z = torch.tensor(omega).float()
+    else the frozen (mean, alpha) pairs.  Returns (z fp32, log_q fp64, bn_stats).  z follows torch's default dtype
+    (float32 unless a caller sets float64 to run the whole stack in double precision)."""
+    z = torch.tensor(omega).to(torch.get_default_dtype())
     log_q = torch.tensor(base_log_density_f64(omega))
     idx = 0
     bn_i = 0

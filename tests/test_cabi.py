@@ -153,3 +153,60 @@ def test_training_entries_host_side():
     assert lib.tnf_flow_forward_train_bwd_f32(n, n, n, n, n, n, n, n, n, n, 1, 1, 64, 8, 2, 2, 15, 100000, 100000, n, 0, n) == EUNSUP
     assert lib.tnf_maf_inverse_alpha(7, n, n, n, n, n, n, 1, 1, 4, 3, 2, 15, 1000, n) == EINVAL  # dtype
     assert b"dtype" in lib.tnf_last_error()
+
+
+# S_max of each narrow coupling kernel per (D, L) at U = 15 and U = 16 (both fill the same 16-unit tiles): the largest
+# num_stages whose operands fit the 160 KB of LDS.  Columns: the whole-flow entry points (tnf_flow_fused_supported: below
+# it TNF_FUSE_FLOW runs a whole-flow kernel, above it TNF_FUSE_AUTO takes the per-layer chain), the default whole-flow
+# kernel flow_fused2 (above it, up to the first column, flow_fused_f16 and its run-time stage loop run instead), its
+# 32-sample-group form flow_fused3 (flow variant 20) and the one-kernel reversible training backward.  A layout change
+# that moves one of these boundaries moves the shapes tests/test_gpu_domain.py sweeps: it must show up here.
+DOMAIN_S_MAX = {  # (D, L): (whole flow, flow_fused2, flow_fused3, reversible backward)
+    (32, 1): (17, 17, 12, 14), (32, 2): (11, 11, 7, 8), (32, 3): (9, 8, 5, 6),
+    (64, 1): (8, 8, 8, 6), (64, 2): (7, 6, 6, 4), (64, 3): (6, 5, 4, 3),
+}
+
+
+def _s_max(pred, D, L, U):
+    S = 0
+    while pred(D, S + 1, L, U):
+        S += 1
+    assert S < 64
+    assert not any(pred(D, s, L, U) for s in range(S + 1, S + 9)), "the predicate is not monotone in S"
+    return S
+
+
+def test_narrow_kernel_domains_host_side():
+    from torch_nf_amd._lib import lib
+
+    preds = (lib.tnf_flow_fused_supported, lib.tnf_flow_fused2_supported, lib.tnf_flow_fused3_supported,
+             lib.tnf_flow_train_rev_supported)
+    for (D, L), want in sorted(DOMAIN_S_MAX.items()):
+        for U in (15, 16):
+            got = tuple(_s_max(p, D, L, U) for p in preds)
+            assert got == want, "D=%d L=%d U=%d: S_max %s, pinned %s" % (D, L, U, got, want)
+            for S in (1, want[0], want[0] + 1):
+                assert lib.tnf_cond_flow_supported(D, S, L, U, 64) == 1
+        for p in preds:  # outside the narrow shapes: no S at all
+            assert p(D, 1, L, 17) == 0 and p(D, 1, 4, 15) == 0 and p(D + 2, 1, L, 15) == 0
+    # the conditional-flow kernel: L <= 5, U <= 16, H in {32, 64, 128}, any S
+    for D in (32, 64):
+        for L in range(1, 6):
+            for H in (32, 64, 128):
+                for S in (1, 5, 20, 100):
+                    assert lib.tnf_cond_flow_supported(D, S, L, 15, H) == 1, (D, S, L, H)
+        assert lib.tnf_cond_flow_supported(D, 1, 6, 15, 64) == 0 and lib.tnf_cond_flow_supported(D, 1, 5, 17, 64) == 0
+        assert lib.tnf_cond_flow_supported(D, 1, 5, 15, 96) == 0
+
+
+def test_diag_families_host_side():
+    from torch_nf_amd import _lib
+
+    lib = _lib.lib
+    fams = [getattr(_lib, n) for n in dir(_lib) if n.startswith("DIAG_") and n != "DIAG_FAMILIES"]
+    assert sorted(fams) == list(range(_lib.DIAG_FAMILIES))
+    text = open(os.path.join(ROOT, "include", "tnf.h")).read()
+    assert "TNF_DIAG_FAMILIES = %d" % _lib.DIAG_FAMILIES in text
+    for f in fams:
+        assert lib.tnf_diag_launch_count(f) >= 0
+    assert lib.tnf_diag_launch_count(_lib.DIAG_FAMILIES) == -1 and lib.tnf_diag_launch_count(-1) == -1

@@ -22,6 +22,9 @@ OPT_REV_VARIANT = 7
 EUNSUPPORTED = -2
 DIAG_BWD_LAYER_FP32, DIAG_BWD_LAYER_F16, DIAG_BWD_GENERIC, DIAG_BWD_FLOW_REV = 0, 1, 2, 3
 DIAG_MAF_BWD_MFMA, DIAG_MAF_BWD_GENERIC, DIAG_BWD_WIDE = 4, 5, 6
+DIAG_FLOW_FUSED2, DIAG_FLOW_FUSED2_FWD, DIAG_FLOW_FUSED3, DIAG_FLOW_F16, DIAG_FLOW_FP32 = 7, 8, 9, 10, 11
+DIAG_FLOW_RANGE2, DIAG_FLOW_RANGE2_FWD, DIAG_COUPLING_MFMA, DIAG_COND_FLOW = 12, 13, 14, 15
+DIAG_FAMILIES = 16
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
@@ -90,6 +93,8 @@ SIGNATURES = {
     "tnf_base_log_density_f64": (ctypes.c_int, [_i32, _vp, _vp, _i64, _i32, _vp]),
     "tnf_flow_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32, _i32, _i32]),
     "tnf_flow_fused_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "tnf_flow_fused2_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "tnf_flow_fused3_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "tnf_flow_log_prob_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32,
                                              _i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
     "tnf_flow_log_prob_diag_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32,

@@ -794,6 +794,14 @@ int tnf_flow_fused_supported(int32_t D, int32_t S, int32_t L, int32_t U) {
     return flow_fused_supported(D, S, L, U) ? 1 : 0;
 }
 
+int tnf_flow_fused2_supported(int32_t D, int32_t S, int32_t L, int32_t U) {
+    return flow_fused2_supported(D, S, L, U) ? 1 : 0;
+}
+
+int tnf_flow_fused3_supported(int32_t D, int32_t S, int32_t L, int32_t U) {
+    return flow_fused3_supported(D, S, L, U) ? 1 : 0;
+}
+
 int64_t tnf_flow_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t S, int32_t L, int32_t U,
                                  int32_t fusion) {
     if (M < 1 || N < 0 || D < 1 || S < 1 || L < 1 || U < 1)

@@ -485,6 +485,7 @@ static int launch_cond_variant(const CondArgs& a, hipStream_t st) {
     const int64_t per_wg = (int64_t)NW * 16 * BT;
     const int64_t blocks = (a.M + per_wg - 1) / per_wg;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "cond_flow: grid too large");
+    diag_count(TNF_DIAG_COND_FLOW);
     hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * NW), smem, st, a);
     return check_launch("cond_flow");
 }

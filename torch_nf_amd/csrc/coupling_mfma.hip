@@ -442,6 +442,7 @@ int launch_coupling_mfma(const MfmaLayerArgs& a, hipStream_t st) {
         return fail(TNF_EUNSUPPORTED, "coupling_mfma: no kernel for D=%d L=%d U=%d", a.D, a.L, a.U);
     const int64_t M = a.Mz > a.Mp ? a.Mz : a.Mp;
     if (a.N <= 0) return TNF_OK;
+    diag_count(TNF_DIAG_COUPLING_MFMA);
     if (a.D == 64) launch_h<32>(a, M, st);
     else launch_h<16>(a, M, st);
     return check_launch("coupling_mfma");

@@ -270,6 +270,7 @@ int launch_flow_fused(const float* z, const float* images, const float* fold, co
     const int64_t M = Mz > Mp ? Mz : Mp;
     if (N <= 0) return TNF_OK;
     FlowFusedArgs a{z, images, fold, ldc, z_out, sum_log_det, log_prob, Mz, Mp, N, S, U};
+    diag_count(TNF_DIAG_FLOW_FP32);
     int rc = (D == 64) ? launch_h<32>(a, L, inverse, M, st) : launch_h<16>(a, L, inverse, M, st);
     if (rc != TNF_OK) return rc;
     return check_launch("flow_fused");

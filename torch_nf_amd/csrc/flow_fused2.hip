@@ -1072,6 +1072,7 @@ int launch_flow_fused2(const float* z, float* z0, float* sum_log_det, float* log
     Flow2Args a{z, z0, sum_log_det, log_prob, Mz, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage,
                 fl.p_up + fl.p_low, fl.p_up, interval_consts, slow_count};
     a.log_q = forward ? log_q : nullptr;
+    diag_count(forward ? TNF_DIAG_FLOW_FUSED2_FWD : TNF_DIAG_FLOW_FUSED2);
     int rc;
     if (D == 64) rc = L == 1 ? launch2_v<32, 1>(a, M, forward, st) : (L == 2 ? launch2_v<32, 2>(a, M, forward, st) : launch2_v<32, 3>(a, M, forward, st));
     else rc = L == 1 ? launch2_v<16, 1>(a, M, forward, st) : (L == 2 ? launch2_v<16, 2>(a, M, forward, st) : launch2_v<16, 3>(a, M, forward, st));
@@ -1090,6 +1091,7 @@ static int launch_range_t(const Range2Args& ra_in, int64_t M, hipStream_t st) {
     ra.dma = (TNF2_RANGE_DMA && staged && smem + slot2 <= 160 * 1024) ? 1 : 0;
     if (ra.dma) smem += slot2;
     const bool hf = (ra.c_hi & 1) != 0, hl = (ra.c_lo & 1) != 0;
+    diag_count(FWD ? TNF_DIAG_FLOW_RANGE2_FWD : TNF_DIAG_FLOW_RANGE2);
     void (*kern)(Range2Args);
     if constexpr (FWD) {
         kern = hf ? flow_range2_kernel<H, L, NT, NW, true, true, 0, true> : flow_range2_kernel<H, L, NT, NW, false, false, 0, true>;

@@ -284,6 +284,7 @@ int launch_flow_fused3(const float* z, float* z0, float* sum_log_det, float* log
     const FlowLayout fl = flow_layout(D, S, L, U);
     Flow2Args a{z, z0, sum_log_det, log_prob, Mz, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage,
                 fl.p_up + fl.p_low, fl.p_up, interval_consts, slow_count};
+    diag_count(TNF_DIAG_FLOW_FUSED3);
     int rc;
     if (D == 64) rc = L == 1 ? launch3_v<32, 1>(a, M, st) : (L == 2 ? launch3_v<32, 2>(a, M, st) : launch3_v<32, 3>(a, M, st));
     else rc = L == 1 ? launch3_v<16, 1>(a, M, st) : (L == 2 ? launch3_v<16, 2>(a, M, st) : launch3_v<16, 3>(a, M, st));

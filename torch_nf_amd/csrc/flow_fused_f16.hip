@@ -506,6 +506,7 @@ int launch_flow_fused_f16(const float* z, const float* images, const float* fold
     const FlowLayout fl = flow_layout(D, S, L, U);
     FlowF16Args a{z, images, fold, ldc, z_out, sum_log_det, log_prob, Mz, Mp, N, mfma_image_floats(D, 3), S,
                   params, bn_mean, bn_alpha, pstride, fl.stage, fl.p_up + fl.p_low, fl.p_up, U, interval_consts};
+    diag_count(TNF_DIAG_FLOW_F16);
     int rc = (D == 64) ? launch16_h<32>(a, L, inverse, M, variant, st) : launch16_h<16>(a, L, inverse, M, variant, st);
     if (rc != TNF_OK) return rc;
     return check_launch("flow_fused_f16");
