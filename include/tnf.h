@@ -105,7 +105,9 @@ enum {
     TNF_DIAG_COUPLING_MFMA = 14,  /* coupling_mfma_kernel: fp32-MFMA layer kernel (layer variant 0 chains, training
                                    * forward of the per-layer pair, bijector-level calls) */
     TNF_DIAG_COND_FLOW = 15,      /* cond_flow_kernel: conditional flow log_prob, training forward and sampling */
-    TNF_DIAG_FAMILIES = 16
+    TNF_DIAG_FLOW_PADDED = 16,    /* flow_fused2_kernel in its padded layouts (tnf_flow_padded_log_prob_f32) */
+    TNF_DIAG_FLOW_PADDED_FWD = 17, /* the same, sampling direction (tnf_flow_padded_forward_f32) */
+    TNF_DIAG_FAMILIES = 18
 };
 int64_t tnf_diag_launch_count(int32_t family);
 
@@ -551,6 +553,33 @@ int tnf_flow_forward_logq_f32(const float* omega, const float* params, const flo
                               int64_t M_p, int64_t N, int32_t D, int32_t num_stages, int32_t num_layers,
                               int32_t num_units, int64_t params_row_stride, int32_t fusion, void* workspace,
                               int64_t workspace_bytes, void* stream);
+
+/* ---- whole-flow kernel at any width: RealNVP stacks with 2 <= D <= 63, D != 32 ---------------------------
+ * The one-kernel path of tnf_flow_log_prob_f32 / tnf_flow_forward_logq_f32 exists for D = 32 and D = 64.  These
+ * entry points run the same kernel with each coupling half zero-padded to 16 (D <= 31) or 32 (D = 33 .. 63)
+ * features; the halves split at D / 2 as in the reference (bijectors.py:157-165), so odd D is covered.  One launch
+ * per call, no host synchronisation and no allocation (capturable in a HIP graph); no fused support layer.
+ * tnf_flow_padded_supported: 1 for 2 <= D <= 63, D != 32, 1 <= num_layers <= 3, 1 <= num_units <= 16 and
+ * num_stages up to the LDS limit (monotone in num_stages), else 0.
+ * z / omega and the outputs need 4-byte alignment only (rows of D floats, contiguous).  params_row_stride as in
+ * tnf_flow_log_prob_f32; M_z and M_p broadcast (1 or M).  The kernel keeps its scratch in LDS; the workspace
+ * (tnf_flow_padded_workspace_bytes) is checked and reserved per context, nothing is read from it.
+ * tnf_flow_padded_log_prob_f32: log_prob (M,N), z0 (M,N,D), sum_log_det (M,N) -- each optional, not all NULL; z0
+ * must not alias z; exact_reruns (may be NULL) as in tnf_flow_log_prob_diag_f32.
+ * tnf_flow_padded_forward_f32: frozen-statistics sampling, z_out (M,N,D), sum_log_det (M,N), and log_q (M,N)
+ * float64 = log N(omega; 0, I) - sum_log_det when log_q is not NULL. */
+int tnf_flow_padded_supported(int32_t D, int32_t num_stages, int32_t num_layers, int32_t num_units);
+int64_t tnf_flow_padded_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t num_stages, int32_t num_layers,
+                                        int32_t num_units);
+int tnf_flow_padded_log_prob_f32(const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
+                                 float* log_prob, float* z0, float* sum_log_det, int64_t M_z, int64_t M_p, int64_t N,
+                                 int32_t D, int32_t num_stages, int32_t num_layers, int32_t num_units,
+                                 int64_t params_row_stride, void* workspace, int64_t workspace_bytes, void* stream,
+                                 uint32_t* exact_reruns);
+int tnf_flow_padded_forward_f32(const float* omega, const float* params, const float* bn_mean, const float* bn_alpha,
+                                float* z_out, float* sum_log_det, double* log_q, int64_t M_z, int64_t M_p, int64_t N,
+                                int32_t D, int32_t num_stages, int32_t num_layers, int32_t num_units,
+                                int64_t params_row_stride, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

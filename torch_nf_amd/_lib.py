@@ -24,7 +24,8 @@ DIAG_BWD_LAYER_FP32, DIAG_BWD_LAYER_F16, DIAG_BWD_GENERIC, DIAG_BWD_FLOW_REV = 0
 DIAG_MAF_BWD_MFMA, DIAG_MAF_BWD_GENERIC, DIAG_BWD_WIDE = 4, 5, 6
 DIAG_FLOW_FUSED2, DIAG_FLOW_FUSED2_FWD, DIAG_FLOW_FUSED3, DIAG_FLOW_F16, DIAG_FLOW_FP32 = 7, 8, 9, 10, 11
 DIAG_FLOW_RANGE2, DIAG_FLOW_RANGE2_FWD, DIAG_COUPLING_MFMA, DIAG_COND_FLOW = 12, 13, 14, 15
-DIAG_FAMILIES = 16
+DIAG_FLOW_PADDED, DIAG_FLOW_PADDED_FWD = 16, 17
+DIAG_FAMILIES = 18
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
@@ -134,6 +135,12 @@ SIGNATURES = {
                                             _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
     "tnf_flow_forward_logq_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
                                                  _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
+    "tnf_flow_padded_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "tnf_flow_padded_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "tnf_flow_padded_log_prob_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
+                                                    _i32, _i32, _i64, _vp, _i64, _vp, _vp]),
+    "tnf_flow_padded_forward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
+                                                   _i32, _i32, _i64, _vp, _i64, _vp]),
 }
 
 

@@ -1436,4 +1436,71 @@ int tnf_flow_forward_logq_f32(const float* omega, const float* params, const flo
                              pstride, fusion, workspace, workspace_bytes, stream, log_q);
 }
 
+// ---- whole-flow kernel in its padded layouts (flow_fused2.hip, PAD) ----
+int tnf_flow_padded_supported(int32_t D, int32_t S, int32_t L, int32_t U) {
+    return flow_padded_supported(D, S, L, U) ? 1 : 0;
+}
+
+int64_t tnf_flow_padded_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t S, int32_t L, int32_t U) {
+    if (M < 1 || N < 0 || D < 1 || S < 1 || L < 1 || U < 1)
+        return fail(TNF_EINVAL, "tnf_flow_padded_workspace_bytes: M=%lld N=%lld D=%d S=%d L=%d U=%d", (long long)M,
+                    (long long)N, D, S, L, U);
+    if (!flow_padded_supported(D, S, L, U))
+        return fail(TNF_EUNSUPPORTED, "tnf_flow_padded_workspace_bytes: no padded kernel for D=%d S=%d L=%d U=%d", D, S, L, U);
+    return round16(M * 16);  // one reserved 16-byte slot per context; the kernel's scratch is its LDS
+}
+
+static int flow_padded_checks(const char* fn, const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
+                              int64_t M_z, int64_t M_p, int64_t N, int D, int S, int L, int U, int64_t pstride, const void* ws,
+                              int64_t ws_bytes) {
+    int rc = check_mnd(fn, M_z, M_p, N, D);
+    if (rc) return rc;
+    if (S < 1 || L < 1 || U < 1) return fail(TNF_EINVAL, "%s: S=%d L=%d U=%d", fn, S, L, U);
+    if (!z || !params || !bn_mean || !bn_alpha) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
+    if (pstride < flow_layout(D, S, L, U).total)
+        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride,
+                    (long long)flow_layout(D, S, L, U).total);
+    if (!flow_padded_supported(D, S, L, U))
+        return fail(TNF_EUNSUPPORTED, "%s: no padded whole-flow kernel for D=%d S=%d L=%d U=%d", fn, D, S, L, U);
+    const int64_t need = tnf_flow_padded_workspace_bytes(M_z > M_p ? M_z : M_p, N, D, S, L, U);
+    if (!ws || ws_bytes < need)
+        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes, (long long)need);
+    return TNF_OK;
+}
+
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+int tnf_flow_padded_log_prob_f32(const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
+                                 float* log_prob, float* z0, float* sum_log_det, int64_t M_z, int64_t M_p, int64_t N,
+                                 int32_t D, int32_t S, int32_t L, int32_t U, int64_t pstride, void* workspace,
+                                 int64_t workspace_bytes, void* stream, uint32_t* exact_reruns) {
+    const char* fn = "tnf_flow_padded_log_prob_f32";
+    int rc = flow_padded_checks(fn, z, params, bn_mean, bn_alpha, M_z, M_p, N, D, S, L, U, pstride, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (!log_prob && !z0 && !sum_log_det) return fail(TNF_EINVAL, "%s: no output requested", fn);
+    if (!aligned4(z) || (z0 && !aligned4(z0)) || (log_prob && !aligned4(log_prob)) || (sum_log_det && !aligned4(sum_log_det)))
+        return fail(TNF_EINVAL, "%s: z and the outputs must be 4-byte aligned", fn);
+    if (z0 == z) return fail(TNF_EINVAL, "%s: z0 must not alias z", fn);
+    if (N == 0) return TNF_OK;
+    return launch_flow_padded(z, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha,
+                              exact_reruns, as_stream(stream), 0, nullptr);
+}
+
+int tnf_flow_padded_forward_f32(const float* omega, const float* params, const float* bn_mean, const float* bn_alpha,
+                                float* z_out, float* sum_log_det, double* log_q, int64_t M_z, int64_t M_p, int64_t N,
+                                int32_t D, int32_t S, int32_t L, int32_t U, int64_t pstride, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    const char* fn = "tnf_flow_padded_forward_f32";
+    int rc = flow_padded_checks(fn, omega, params, bn_mean, bn_alpha, M_z, M_p, N, D, S, L, U, pstride, workspace,
+                                workspace_bytes);
+    if (rc) return rc;
+    if (!z_out || !sum_log_det) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
+    if (!aligned4(omega) || !aligned4(z_out) || !aligned4(sum_log_det) || (log_q && (reinterpret_cast<uintptr_t>(log_q) & 7u)))
+        return fail(TNF_EINVAL, "%s: omega and the outputs must be 4-byte aligned (log_q 8-byte)", fn);
+    if (z_out == omega) return fail(TNF_EINVAL, "%s: z_out must not alias omega", fn);
+    if (N == 0) return TNF_OK;
+    return launch_flow_padded(omega, z_out, sum_log_det, nullptr, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha,
+                              nullptr, as_stream(stream), 1, log_q);
+}
+
 }  // extern "C"

@@ -149,21 +149,23 @@ static_assert(Img2<32, 3>::FLOATS % 4 == 0 && Img2<16, 1>::FLOATS % 4 == 0, "ima
 
 // kappa of a layer: its layer-0 weights, with the activation folding (2 log2 e) and the fold A in front of the
 // conditioner half, scaled by 2^kappa have their largest magnitude in [1, 2).  One wave.
+// din: the real conditioner width (padded layouts: the rows beyond it are zero and do not count).
 template <int H>
-__device__ __forceinline__ int layer_kappa(const float* __restrict__ p, int U, int lane, const float* foldc, int c) {
+__device__ __forceinline__ int layer_kappa(const float* __restrict__ p, int U, int lane, const float* foldc, int c,
+                                           int din = H) {
     constexpr int D = 2 * H;
     constexpr int HT = H / 16;
     const int r = lane & 15, q = lane >> 4;
     const int coff = (c & 1) ? H : 0;
     const float* wt = p;
-    const float* ws = p + H * U;
+    const float* ws = p + din * U;
     float mx = 0.f;
 #pragma unroll
     for (int m = 0; m < HT; ++m)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int f = 16 * m + 4 * q + j;
-            const bool ok = r < U;
+            const bool ok = r < U && f < din;
             const float a = foldc[coff + f];
             mx = fmaxf(mx, fabsf(kTwoLog2e * ld_sel(wt, f * U + r, ok) * a));
             mx = fmaxf(mx, fabsf(kTwoLog2e * ld_sel(ws, f * U + r, ok) * a));
@@ -189,14 +191,17 @@ __device__ __forceinline__ void store_k16(u4* gd, const float (&v)[4]) {
 //   sc_in    2^kappa_k: the conditioner registers hold (true value before foldc) / sc_in
 //   sc_prev  2^kappa_{k-1} (ignored when foldprev == NULL)
 //   sig_next 2^-kappa_{k+1}: factor the transformed half is emitted with (1 for the last layer walked)
+//   din/dout real conditioner / transformed widths (< H only in the padded layouts: zero weight rows and columns, so
+//            padded s and t outputs are exactly 0; foldc / foldprev must be the identity on the padded features)
 template <int H, int L, int PREC = 0, bool FWD = false>
 __device__ __forceinline__ void build_image2(float* img, const float* __restrict__ p, int U, int lane, const float* foldc,
-                                             const float* foldprev, int c, float sc_in, float sc_prev, float sig_next) {
+                                             const float* foldprev, int c, float sc_in, float sc_prev, float sig_next,
+                                             int din = H, int dout = H) {
     typedef Img2<H, L> I;
     constexpr int D = 2 * H;
     constexpr int HT = I::HT;
     LayerW<H, L> w;
-    load_layer_w<H, L>(w, p, U, lane);
+    load_layer_w<H, L>(w, p, U, lane, din, dout);
     const int q = lane >> 4;
     const int coff = (c & 1) ? H : 0, toff = (c & 1) ? 0 : H;
 

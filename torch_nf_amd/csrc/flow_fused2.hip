@@ -60,6 +60,9 @@
 #ifndef TNF2_UNROLL
 #define TNF2_UNROLL 1  // num_stages = 4: layer loop fully unrolled (every LDS operand offset an immediate)
 #endif
+#ifndef TNF2_PAD_UNROLL32
+#define TNF2_PAD_UNROLL32 0  // 1: ... also in the padded H = 32 layout (spills)
+#endif
 
 namespace tnf {
 
@@ -106,12 +109,26 @@ __device__ __forceinline__ void run_layers2(const float* img, int S, int lane, f
 // FWD = false: the inverse pass (z -> z0, log_prob), walking layers 2S-1 .. 0 with the folds in FRONT of the layers.
 // FWD = true: the sampling pass (omega -> z, sum of log-dets), walking 0 .. 2S-1 with the folds BEHIND the layers:
 // fold slot c holds the map in front of layer c in the walk -- slot 0 the identity, slot c the forward fold of layer c-1.
-template <int H, int L, int NT, int NWAVES, int SS = 0, bool FWD = false>
+//
+// PAD = true: any real width a.Dr in 2 .. 2H-1.  The registers, the LDS folds and the operand
+// images keep the 2H-wide layout; the lower register half holds features 0 .. h-1 (h = Dr / 2), the upper half
+// features h .. Dr-1 (bijectors.py's split for every layer), both zero-padded to H.  Padding is exact: zero weight rows
+// and columns (build_image2's din / dout), identity folds on the padded features, zero inputs -- padded features stay 0
+// and add 0 to every sum.  Rows (Dr floats each, 4-byte aligned) enter and leave through a wave-private LDS staging
+// tile of 16 rows; no fused support layer.
+__device__ __forceinline__ int pad_feature(int pf, int H, int h, int Dr) {  // padded index -> real feature, -1: padding
+    if (pf < H) return pf < h ? pf : -1;
+    return pf - H < Dr - h ? h + pf - H : -1;
+}
+
+template <int H, int L, int NT, int NWAVES, int SS = 0, bool FWD = false, bool PAD = false>
 __global__ void __launch_bounds__(NWAVES * 64)
 flow_fused2_kernel(Flow2Args a) {
     constexpr int D = 2 * H;
     constexpr int HT = H / 16;
     typedef Img2<H, L> I;
+    const int Dr = PAD ? a.Dr : D;  // real row width (global memory); D: the register / LDS layout
+    const int hr = Dr / 2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int nl = 2 * a.S;
     float* img = lds;
@@ -136,8 +153,14 @@ flow_fused2_kernel(Flow2Args a) {
     {
         float acc = 0.f;
         for (int i = threadIdx.x; i < nl * D; i += NWAVES * 64) {
-            const int c = i / D, d = i - c * D;
-            const float alpha = a.bn_alpha[c * D + d], mu = a.bn_mean[c * D + d];
+            const int c = i / D, pd = i - c * D;
+            const int d = PAD ? pad_feature(pd, H, hr, Dr) : pd;
+            if (PAD && d < 0) {  // padded feature: identity map, no log-det
+                fold[(FWD ? c + 1 : c) * 2 * D + pd] = 1.f;
+                fold[(FWD ? c + 1 : c) * 2 * D + D + pd] = 0.f;
+                continue;
+            }
+            const float alpha = a.bn_alpha[c * Dr + d], mu = a.bn_mean[c * Dr + d];
             acc -= logf(alpha);
             float ea = 1.f, shift = 0.f;
             if (c & 1) {
@@ -145,16 +168,16 @@ flow_fused2_kernel(Flow2Args a) {
                 const float av = ap[d];
                 acc += av;
                 ea = expf(av);
-                shift = ap[D + d];
+                shift = ap[Dr + d];
             }
             if constexpr (FWD) {  // A = e^a / alpha_bn, B = shift - mean_bn A, behind layer c: slot c + 1
                 const float A = ea / alpha;
-                fold[(c + 1) * 2 * D + d] = A;
-                fold[(c + 1) * 2 * D + D + d] = shift - mu * A;
+                fold[(c + 1) * 2 * D + pd] = A;
+                fold[(c + 1) * 2 * D + D + pd] = shift - mu * A;
             } else {
                 const float A = alpha / ea;
-                fold[c * 2 * D + d] = A;
-                fold[c * 2 * D + D + d] = mu - shift * A;
+                fold[c * 2 * D + pd] = A;
+                fold[c * 2 * D + D + pd] = mu - shift * A;
             }
         }
         if constexpr (FWD)
@@ -167,8 +190,12 @@ flow_fused2_kernel(Flow2Args a) {
     }
     __syncthreads();
     // ---- prologue B: the scale exponent of every layer's conditioner input ----
+    // real widths of layer c (bijectors.py:157-165): even layers condition on the lower half, odd ones on the upper
+    auto d_cond = [&](int c) -> int { return PAD ? ((c & 1) ? Dr - hr : hr) : H; };
+    auto d_tran = [&](int c) -> int { return PAD ? ((c & 1) ? hr : Dr - hr) : H; };
     for (int c = wave; c < nl; c += NWAVES) {
-        const int kc = layer_kappa<H>(prow + (c >> 1) * a.stage_stride + (c & 1) * a.low_off, a.U, lane, fold + c * 2 * D, c);
+        const int kc = layer_kappa<H>(prow + (c >> 1) * a.stage_stride + (c & 1) * a.low_off, a.U, lane, fold + c * 2 * D, c,
+                                      d_cond(c));
         if (lane == 0) kap[c] = kc;
     }
     __syncthreads();
@@ -182,13 +209,14 @@ flow_fused2_kernel(Flow2Args a) {
             const float sc_prev = c > 0 ? pow2i(kap[c - 1]) : 1.f;
             const float sig_next = c < nl - 1 ? pow2i(-kap[c + 1]) : 1.f;
             build_image2<H, L, 0, true>(img + c * I::FLOATS, pl, a.U, lane, fold + c * 2 * D,
-                                        c > 0 ? fold + (c - 1) * 2 * D : nullptr, c, sc_in, sc_prev, sig_next);
+                                        c > 0 ? fold + (c - 1) * 2 * D : nullptr, c, sc_in, sc_prev, sig_next, d_cond(c),
+                                        d_tran(c));
         } else {
             const bool first = (c == nl - 1), last = (c == 0);
             const float sc_prev = first ? 1.f : pow2i(kap[c + 1]);
             const float sig_next = last ? 1.f : pow2i(-kap[c - 1]);
             build_image2<H, L>(img + c * I::FLOATS, pl, a.U, lane, fold + c * 2 * D,
-                               first ? nullptr : fold + (c + 1) * 2 * D, c, sc_in, sc_prev, sig_next);
+                               first ? nullptr : fold + (c + 1) * 2 * D, c, sc_in, sc_prev, sig_next, d_cond(c), d_tran(c));
         }
     }
     if constexpr (FWD) {
@@ -208,7 +236,7 @@ flow_fused2_kernel(Flow2Args a) {
             fin[D + f] = fold[D + f];
         }
     }
-    const bool has_iv = a.iv != nullptr;
+    const bool has_iv = !PAD && a.iv != nullptr;
     __syncthreads();
 
 #if TNF2_PRIO
@@ -216,8 +244,8 @@ flow_fused2_kernel(Flow2Args a) {
 #endif
     // the first layer walked conditions on the upper half (inverse: c = nl-1) / the lower half (forward: c = 0)
     const float presc = pow2i(-kap[FWD ? 0 : nl - 1]);
-    const float* zb = a.z + mz * a.N * D;
-    float* zo = a.z_out ? a.z_out + m * a.N * D : nullptr;
+    const float* zb = a.z + mz * a.N * Dr;
+    float* zo = a.z_out ? a.z_out + m * a.N * Dr : nullptr;
     float* sldo = a.sum_log_det ? a.sum_log_det + m * a.N : nullptr;
     float* lpo = a.log_prob ? a.log_prob + m * a.N : nullptr;
     float ldc = 0.f;
@@ -242,6 +270,65 @@ flow_fused2_kernel(Flow2Args a) {
                 dlo[t][mm] = *reinterpret_cast<const f4*>(zr + 16 * mm);
                 dhi[t][mm] = *reinterpret_cast<const f4*>(zr + H + 16 * mm);
             }
+        }
+    };
+    // PAD: a 16-row tile is 16 Dr floats, contiguous, loaded as it lies (KR coalesced 4-byte loads per lane) and kept in
+    // registers while the group before it runs; unstaged through the wave's LDS tile, whose row stride SP is odd so that
+    // the fragment reads (16 rows x 4 lane groups) spread over the banks
+    constexpr int KR = D / 4;  // 16 x 2H floats / 64 lanes >= 16 Dr / 64
+    const int SP = Dr | 1;
+    float* stg_p = stage + wave * 16 * D;
+    const float rDr = 1.f / (float)Dr;
+    auto pad_slot = [&](int idx) -> int {  // tile offset idx = row Dr + col -> staging offset row SP + col
+        const int r = (int)(((float)idx + 0.5f) * rDr);
+        return idx + r * (SP - Dr);
+    };
+    auto tile_floats = [&](int64_t row0) -> int {
+        const int64_t nr = a.N - row0;
+        return nr <= 0 ? 0 : (int)(nr < 16 ? nr : 16) * Dr;
+    };
+    auto load_raw = [&](int64_t g, float (&raw)[NT][KR]) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int64_t row0 = (g * NT + t) * 16;
+            const int nf = tile_floats(row0);
+            const float* src = zb + (nf > 0 ? row0 * Dr : 0);
+#pragma unroll
+            for (int k = 0; k < KR; ++k) raw[t][k] = ld_sel(src, k * 64 + lane, k * 64 + lane < nf);
+        }
+    };
+    auto unstage = [&](const float (&raw)[NT][KR], f4 (&dlo)[NT][HT], f4 (&dhi)[NT][HT]) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+#pragma unroll
+            for (int k = 0; k < KR; ++k)
+                if (k * 64 + lane < 16 * Dr) stg_p[pad_slot(k * 64 + lane)] = raw[t][k];
+#pragma unroll
+            for (int mm = 0; mm < HT; ++mm)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int f = 16 * mm + 4 * q + j;
+                    const float* sr = stg_p + s * SP;
+                    dlo[t][mm][j] = f < hr ? sr[f] : 0.f;
+                    dhi[t][mm][j] = f < Dr - hr ? sr[hr + f] : 0.f;
+                }
+        }
+    };
+    // the exact re-run reloads its group straight into the fragment layout (rare; keeps the registers of the next group)
+    auto load_frag = [&](int64_t g, f4 (&dlo)[NT][HT], f4 (&dhi)[NT][HT]) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            int64_t row = (g * NT + t) * 16 + s;
+            if (row >= a.N) row = a.N - 1;
+            const float* zr = zb + row * Dr;
+#pragma unroll
+            for (int mm = 0; mm < HT; ++mm)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int f = 16 * mm + 4 * q + j;
+                    dlo[t][mm][j] = ld_sel(zr, f, f < hr);
+                    dhi[t][mm][j] = ld_sel(zr + hr, f, f < Dr - hr);
+                }
         }
     };
     // support layer (first bijector of the inverse pass) and the first layer's input scale
@@ -297,7 +384,9 @@ flow_fused2_kernel(Flow2Args a) {
     };
 
     f4 nlo[NT][HT], nhi[NT][HT];
-    load_group(grp, nlo, nhi);
+    float nraw[NT][KR];
+    if constexpr (PAD) load_raw(grp, nraw);
+    else load_group(grp, nlo, nhi);
 #if TNF2_STAMP  // diagnostic build only (tools/clock_probe.py): shader clock under this kernel's own load
     const unsigned long long st_c0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -309,15 +398,17 @@ flow_fused2_kernel(Flow2Args a) {
         const bool has_next = nxt < g_hi;
         f4 lo[NT][HT], hi[NT][HT];
         float ssum[NT], ssup[NT];  // ssup: log-det of the fused support layer (natural log, this lane's features)
+        if constexpr (PAD) unstage(nraw, lo, hi);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             ssum[t] = 0.f;
             ssup[t] = 0.f;
+            if constexpr (!PAD)
 #pragma unroll
-            for (int mm = 0; mm < HT; ++mm) {
-                lo[t][mm] = nlo[t][mm];
-                hi[t][mm] = nhi[t][mm];
-            }
+                for (int mm = 0; mm < HT; ++mm) {
+                    lo[t][mm] = nlo[t][mm];
+                    hi[t][mm] = nhi[t][mm];
+                }
         }
         double bsq[NT];  // sampling pass with a.log_q: this lane's share of |omega|^2, float64 like the reference's base density
         if constexpr (FWD) {
@@ -337,7 +428,10 @@ flow_fused2_kernel(Flow2Args a) {
             }
         }
         enter(lo, hi, ssup);
-        if (has_next) load_group(nxt, nlo, nhi);
+        if (has_next) {
+            if constexpr (PAD) load_raw(nxt, nraw);
+            else load_group(nxt, nlo, nhi);
+        }
         run_layers2<H, L, NT, SS, false, FWD>(img, a.S, lane, lo, hi, ssum);
         // an input beyond the f16 range of its (scaled) operand turned into NaN and reached the log-det sum:
         // re-run this group with exact first-layer contractions (also taken, harmlessly, by genuine NaN inputs)
@@ -345,7 +439,8 @@ flow_fused2_kernel(Flow2Args a) {
 #pragma unroll
         for (int t = 1; t < NT; ++t) chk += ssum[t];
         if (__builtin_expect(__any(chk != chk), 0)) {
-            load_group(grp, lo, hi);
+            if constexpr (PAD) load_frag(grp, lo, hi);
+            else load_group(grp, lo, hi);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 ssum[t] = 0.f;
@@ -371,7 +466,7 @@ flow_fused2_kernel(Flow2Args a) {
                         sq = __builtin_fmaf(hi[t][mm][j], hi[t][mm][j], sq);
                     }
                 sq = reduce_q(sq);
-                if (q == 0 && row_ok) lpo[row] = -0.5f * sq - (float)D * 0.91893853320467274178f - ld_tot;
+                if (q == 0 && row_ok) lpo[row] = -0.5f * sq - (float)Dr * 0.91893853320467274178f - ld_tot;
             }
             if (sldo && q == 0 && row_ok) sldo[row] = ld_tot;
             if constexpr (FWD) {
@@ -380,10 +475,28 @@ flow_fused2_kernel(Flow2Args a) {
                     b += __shfl_xor(b, 16);
                     b += __shfl_xor(b, 32);
                     if (q == 0 && row_ok)
-                        a.log_q[m * a.N + row] = (-0.5 * b - (double)D * 0.91893853320467274178) - (double)ld_tot;
+                        a.log_q[m * a.N + row] = (-0.5 * b - (double)Dr * 0.91893853320467274178) - (double)ld_tot;
                 }
             }
-            if (zo && !a.stage_out && row_ok) {
+            if (PAD && zo) {
+                // the real features into the staging tile, then the tile's 16 Dr floats out as they lie
+                const int64_t row0 = (grp * NT + t) * 16;
+                const int nf = tile_floats(row0);
+                float* sr = stg_p + s * SP;
+#pragma unroll
+                for (int mm = 0; mm < HT; ++mm)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int f = 16 * mm + 4 * q + j;
+                        if (f < hr) sr[f] = lo[t][mm][j];
+                        if (f < Dr - hr) sr[hr + f] = hi[t][mm][j];
+                    }
+                float* dst = zo + row0 * Dr;
+#pragma unroll
+                for (int k = 0; k < KR; ++k)
+                    if (k * 64 + lane < nf) dst[k * 64 + lane] = stg_p[pad_slot(k * 64 + lane)];
+            }
+            if (!PAD && zo && !a.stage_out && row_ok) {
                 float* zr = zo + row * D + 4 * q;
 #pragma unroll
                 for (int mm = 0; mm < HT; ++mm) {
@@ -391,7 +504,7 @@ flow_fused2_kernel(Flow2Args a) {
                     *reinterpret_cast<f4*>(zr + H + 16 * mm) = hi[t][mm];
                 }
             }
-            if (zo && a.stage_out) {
+            if (!PAD && zo && a.stage_out) {
                 // rows leave through a wave-private swizzled staging tile, 1 KB (whole 128-B lines) per instruction and
                 // around the caches: straight from the fragment layout (64 B per lane group) the stores cost the kernel
                 // 0.036 ms at D = 64 (0.227 -> 0.263), this way ... (the layer-range kernel's recipe, below)
@@ -1031,15 +1144,15 @@ bool flow_fused2_supported(int D, int S, int L, int U) {
     return flow2_lds_bytes_rt(D, S, L) <= 160 * 1024;
 }
 
-template <int H, int L, int NT, int NW, int SS, bool FWD>
+template <int H, int L, int NT, int NW, int SS, bool FWD, bool PAD = false>
 static int launch2_t(const Flow2Args& a, int64_t M, hipStream_t st) {
     size_t smem = flow2_lds_bytes<H, L>(a.S);
     Flow2Args b = a;
     // row output (z0 / z): through the staging tiles when they fit beside the operand images (D = 64 only: 128-B rows gain nothing)
     const size_t stage_bytes = (size_t)NW * 16 * 2 * H * sizeof(float);
-    b.stage_out = (H == 32 && a.z_out != nullptr && smem + stage_bytes <= 160 * 1024 && TNF2_FUSED_STAGE) ? 1 : 0;
-    if (b.stage_out) smem += stage_bytes;
-    auto kern = flow_fused2_kernel<H, L, NT, NW, SS, FWD>;
+    b.stage_out = (!PAD && H == 32 && a.z_out != nullptr && smem + stage_bytes <= 160 * 1024 && TNF2_FUSED_STAGE) ? 1 : 0;
+    if (b.stage_out || PAD) smem += stage_bytes;  // PAD: every row goes in and out through the staging tiles
+    auto kern = flow_fused2_kernel<H, L, NT, NW, SS, FWD, PAD>;
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
         return fail(TNF_ELAUNCH, "flow_fused2: cannot reserve %zu B of LDS", smem);
     const int64_t ngroups = (a.N + 16 * NT - 1) / (16 * NT);
@@ -1050,14 +1163,16 @@ static int launch2_t(const Flow2Args& a, int64_t M, hipStream_t st) {
     return TNF_OK;
 }
 
-template <int H, int L>
+template <int H, int L, bool PAD = false>
 static int launch2_v(const Flow2Args& a, int64_t M, int forward, hipStream_t st) {
-    // the reference's usual depth (num_stages = 4): layer loop fully unrolled
+    // the reference's usual depth (num_stages = 4): layer loop fully unrolled -- not in the padded H = 32 layout, whose
+    // staging registers push the unrolled form past 256 VGPRs (14 - 222 spilled; the run-time loop spills none)
     constexpr int NW = H == 16 ? TNF2_NW16 : TNF2_NW;
 #if TNF2_UNROLL
-    if (a.S == 4) return forward ? launch2_t<H, L, TNF2_NT, NW, 4, true>(a, M, st) : launch2_t<H, L, TNF2_NT, NW, 4, false>(a, M, st);
+    if (a.S == 4 && (!(PAD && H == 32) || TNF2_PAD_UNROLL32))
+        return forward ? launch2_t<H, L, TNF2_NT, NW, 4, true, PAD>(a, M, st) : launch2_t<H, L, TNF2_NT, NW, 4, false, PAD>(a, M, st);
 #endif
-    return forward ? launch2_t<H, L, TNF2_NT, NW, 0, true>(a, M, st) : launch2_t<H, L, TNF2_NT, NW, 0, false>(a, M, st);
+    return forward ? launch2_t<H, L, TNF2_NT, NW, 0, true, PAD>(a, M, st) : launch2_t<H, L, TNF2_NT, NW, 0, false, PAD>(a, M, st);
 }
 
 int launch_flow_fused2(const float* z, float* z0, float* sum_log_det, float* log_prob, int64_t Mz, int64_t Mp, int64_t N,
@@ -1078,6 +1193,44 @@ int launch_flow_fused2(const float* z, float* z0, float* sum_log_det, float* log
     else rc = L == 1 ? launch2_v<16, 1>(a, M, forward, st) : (L == 2 ? launch2_v<16, 2>(a, M, forward, st) : launch2_v<16, 3>(a, M, forward, st));
     if (rc != TNF_OK) return rc;
     return check_launch("flow_fused2");
+}
+
+// ---- padded layouts: H = 16 for D <= 31, H = 32 for D = 33 .. 63; the LDS of the D = 2H kernel plus the staging tiles
+static int pad_half(int D) { return D <= 31 ? 16 : 32; }
+
+static size_t flow_padded_lds_bytes(int D, int S, int L) {
+    const int H = pad_half(D);
+    const int NW = H == 16 ? TNF2_NW16 : TNF2_NW;
+    return flow2_lds_bytes_rt(2 * H, S, L) + (size_t)NW * 16 * 2 * H * sizeof(float);
+}
+
+bool flow_padded_supported(int D, int S, int L, int U) {
+    if (D < 2 || D > 63 || D == 32 || L < 1 || L > 3 || U < 1 || U > 16 || S < 1) return false;
+    return flow_padded_lds_bytes(D, S, L) <= 160 * 1024;
+}
+
+int launch_flow_padded(const float* z, float* z_out, float* sum_log_det, float* log_prob, int64_t Mz, int64_t Mp, int64_t N,
+                       int D, int S, int L, int U, const float* params, int64_t pstride, const float* bn_mean,
+                       const float* bn_alpha, unsigned* slow_count, hipStream_t st, int forward, double* log_q) {
+    if (!flow_padded_supported(D, S, L, U))
+        return fail(TNF_EUNSUPPORTED, "flow_padded: no kernel for D=%d S=%d L=%d U=%d", D, S, L, U);
+    if (N <= 0) return TNF_OK;
+    const int64_t M = Mz > Mp ? Mz : Mp;
+    const FlowLayout fl = flow_layout(D, S, L, U);
+    Flow2Args a{z, z_out, sum_log_det, log_prob, Mz, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage,
+                fl.p_up + fl.p_low, fl.p_up, nullptr, slow_count};
+    a.log_q = forward ? log_q : nullptr;
+    a.Dr = D;
+    diag_count(forward ? TNF_DIAG_FLOW_PADDED_FWD : TNF_DIAG_FLOW_PADDED);
+    int rc;
+    if (pad_half(D) == 32)
+        rc = L == 1 ? launch2_v<32, 1, true>(a, M, forward, st)
+                    : (L == 2 ? launch2_v<32, 2, true>(a, M, forward, st) : launch2_v<32, 3, true>(a, M, forward, st));
+    else
+        rc = L == 1 ? launch2_v<16, 1, true>(a, M, forward, st)
+                    : (L == 2 ? launch2_v<16, 2, true>(a, M, forward, st) : launch2_v<16, 3, true>(a, M, forward, st));
+    if (rc != TNF_OK) return rc;
+    return check_launch("flow_padded");
 }
 
 

@@ -113,24 +113,26 @@ struct LayerW {
 // Gather the operands of lane (r = lane&15, q = lane>>4) from the reference's packed
 // parameter row (bijectors.py:222-235): per MLP layer [W_t | W_s | b_t | b_s], W[in][out].
 // Must be called by a full wave (the column sums use cross-lane shuffles).
+// din / dout: the layer's real conditioner / transformed widths when they are narrower than the H-wide tile (odd or
+// padded D, flow_fused2.hip PAD); the missing rows and columns are zero.
 template <int H, int L>
 __device__ __forceinline__ void load_layer_w(LayerW<H, L>& w, const float* __restrict__ p, int U,
-                                             int lane) {
+                                             int lane, int din = H, int dout = H) {
     constexpr int HT = LayerW<H, L>::HT;
     const int r = lane & 15, q = lane >> 4;
     const bool r_ok = r < U;
     // layer 0: H -> U, feeds a tanh: scale by c
     {
         const float* wt = p;
-        const float* ws = p + H * U;
-        const float* bt = p + 2 * H * U;
+        const float* ws = p + din * U;
+        const float* bt = p + 2 * din * U;
         const float* bs = bt + U;
 #pragma unroll
         for (int m = 0; m < HT; ++m)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int f = 16 * m + 4 * q + j;
-                const bool ok = r_ok && f < H;
+                const bool ok = r_ok && f < din;
                 w.w0[0][m * 4 + j] = kTwoLog2e * ld_sel(wt, f * U + r, ok);
                 w.w0[1][m * 4 + j] = kTwoLog2e * ld_sel(ws, f * U + r, ok);
             }
@@ -175,9 +177,9 @@ __device__ __forceinline__ void load_layer_w(LayerW<H, L>& w, const float* __res
     // output layer: U -> H, consumes r; t plain, s scaled by log2(e)
     {
         const float* wt = p;
-        const float* ws = p + U * H;
-        const float* bt = p + 2 * U * H;
-        const float* bs = bt + H;
+        const float* ws = p + U * dout;
+        const float* bt = p + 2 * U * dout;
+        const float* bs = bt + dout;
 #pragma unroll
         for (int mo = 0; mo < HT; ++mo) {
             float ct = 0.f, cs = 0.f;
@@ -185,9 +187,9 @@ __device__ __forceinline__ void load_layer_w(LayerW<H, L>& w, const float* __res
             for (int j = 0; j < 4; ++j) {
                 const int k = 4 * q + j;
                 const int o = 16 * mo + r;
-                const bool ok = k < U && o < H;
-                const float a = ld_sel(wt, k * H + o, ok);
-                const float b = ld_sel(ws, k * H + o, ok);
+                const bool ok = k < U && o < dout;
+                const float a = ld_sel(wt, k * dout + o, ok);
+                const float b = ld_sel(ws, k * dout + o, ok);
                 ct += a;
                 cs += b;
                 w.w2[0][mo][j] = -2.f * a;
@@ -200,8 +202,8 @@ __device__ __forceinline__ void load_layer_w(LayerW<H, L>& w, const float* __res
                 const int rr = 4 * q + j;  // row inside the 16-feature tile held by this lane
                 const int ob = 16 * mo + rr;
                 const float st = __shfl(ct, rr), ss = __shfl(cs, rr);
-                w.b2[0][mo][j] = ob < H ? ld_sel(bt, ob, ob < H) + st : 0.f;
-                w.b2[1][mo][j] = ob < H ? kLog2e * (ld_sel(bs, ob, ob < H) + ss) : 0.f;
+                w.b2[0][mo][j] = ob < dout ? ld_sel(bt, ob, ob < dout) + st : 0.f;
+                w.b2[1][mo][j] = ob < dout ? kLog2e * (ld_sel(bs, ob, ob < dout) + ss) : 0.f;
             }
         }
     }

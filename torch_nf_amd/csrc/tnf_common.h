@@ -159,6 +159,7 @@ struct Flow2Args {
     int stage_out;         // set by the launcher: row outputs leave through LDS staging tiles (flow_fused2.hip)
     double* log_q;         // sampling pass, optional: log N(omega; 0, I) - (sum of log-dets), (M, N) float64 -- the
                            // log-density NormFlow.forward returns beside the samples (density_estimator.py:369-388)
+    int Dr;                // padded-layout kernel only: the real row width (2 .. 2H-1)
 };
 
 bool flow_fused2_supported(int D, int S, int L, int U);
@@ -168,6 +169,12 @@ int launch_flow_fused2(const float* z, float* z0, float* sum_log_det, float* log
                        const float* bn_alpha, const float* interval_consts, unsigned* slow_count, hipStream_t st,
                        int forward = 0, double* log_q = nullptr);
 // the same tile code as a chain of launches with `per_launch` coupling layers each (1 = one kernel per coupling layer)
+// the same kernel in its padded layouts (flow_fused2.hip, PAD): every D in 2 .. 63 but 32, one launch per call, no
+// fused support layer.  forward as above; log_q (forward only) optional.
+bool flow_padded_supported(int D, int S, int L, int U);
+int launch_flow_padded(const float* z, float* z_out, float* sum_log_det, float* log_prob, int64_t Mz, int64_t Mp, int64_t N,
+                       int D, int S, int L, int U, const float* params, int64_t pstride, const float* bn_mean,
+                       const float* bn_alpha, unsigned* slow_count, hipStream_t st, int forward, double* log_q);
 bool flow_fused3_supported(int D, int S, int L, int U);  // flow_fused3.hip: the same on 32-sample groups (32x32x16 MFMAs)
 int launch_flow_fused3(const float* z, float* z0, float* sum_log_det, float* log_prob, int64_t Mz, int64_t Mp, int64_t N,
                        int D, int S, int L, int U, const float* params, int64_t pstride, const float* bn_mean,

@@ -228,6 +228,22 @@ class NormFlow(DensityEstimator):
             return False
         return ops.has_fast_path(self.D, self.num_layers, self.num_units)
 
+    def _padded_ok(self, z, params):
+        """One-call whole-flow kernel in its padded layouts (every 2 <= D <= 63 but 32, num_units <= 16): the
+        conditions of `_fused_ok`, a 3-d z, and the fusion setting AUTO or FLOW -- FUSE_LAYER keeps the per-layer
+        routes of these shapes (the wide chain, or the per-bijector composition)."""
+        if self.arch_type != "coupling" or self._stats_in_graph() or z.dim() != 3:
+            return False
+        if z.dtype != torch.float32 or params.dtype != torch.float32:
+            return False
+        if torch.is_grad_enabled() and (z.requires_grad or params.requires_grad):
+            return False
+        if params.size(0) > 1 and z.size(1) < 32:
+            return False
+        if self.fusion not in (_lib.FUSE_AUTO, _lib.FUSE_FLOW):
+            return False
+        return ops.flow_padded_supported(self.D, self.num_stages, self.num_layers, self.num_units)
+
     # -- sampling -----------------------------------------------------------
     def __call__(self, N=100, params=None, freeze_bn=False):
         if not self.conditioner:
@@ -265,7 +281,7 @@ class NormFlow(DensityEstimator):
             z = omega.detach().to(dev)  # device-side draw: no float64 round trip
             # the base density of a float32 draw can come out of the whole-flow sampling kernel itself (below);
             # every other route evaluates it here
-            if not (freeze_bn and self._fused_ok(z, p_dev) and self._whole_flow()):
+            if not (freeze_bn and (self._padded_ok(z, p_dev) or (self._fused_ok(z, p_dev) and self._whole_flow()))):
                 log_q = ops.base_log_density_f64(z)
         else:
             if torch.is_tensor(omega):
@@ -287,6 +303,15 @@ class NormFlow(DensityEstimator):
             z, sld = ops.ar_flow_forward_raw(z, p_dev, *self._ar_args(), interval_consts=sup)
             log_q = log_q - sld
             support_done = True
+        elif freeze_bn and self._padded_ok(z, p_dev):
+            # the padded whole-flow kernel (no fused support layer: it runs below as its own kernel)
+            mean, alpha = self._bn_stats(dev)
+            args = (mean, alpha, self.D, self.num_stages, self.num_layers, self.num_units)
+            if log_q is None:
+                z, sld, log_q = ops.flow_padded_forward_raw(z, p_dev, *args, want_log_q=True)
+            else:
+                z, sld = ops.flow_padded_forward_raw(z, p_dev, *args)
+                log_q = log_q - sld
         elif freeze_bn and self._fused_ok(z, p_dev):
             mean, alpha = self._bn_stats(dev)
             fuse_sup = (sup is not None and sup is not False and self._whole_flow())
@@ -348,6 +373,11 @@ class NormFlow(DensityEstimator):
         if self._n_core == len(self.bijectors) and self._ar_fused_ok(z, params):
             _, z0, sld = ops.ar_flow_log_prob_raw(z, params, *self._ar_args(), want_lp=False, want_z0=True, want_sld=True)
             return z0, sld
+        if self._n_core == len(self.bijectors) and self._padded_ok(z, params):
+            mean, alpha = self._bn_stats(_lib.require_device())
+            _, z0, sld = ops.flow_padded_log_prob_raw(z, params, mean, alpha, self.D, self.num_stages, self.num_layers,
+                                                      self.num_units, want_z0=True, want_sld=True, want_lp=False)
+            return z0, sld
         if self._n_core == len(self.bijectors) and self._fused_ok(z, params):
             dev = _lib.require_device()
             mean, alpha = self._bn_stats(dev)
@@ -396,7 +426,7 @@ class NormFlow(DensityEstimator):
             if sup is not False and self._ar_train_ok(z, params):
                 masks, mean, alpha, D, L, U = self._ar_args()
                 return ops.ar_flow_log_prob_train(z, params, masks, mean, alpha, sup, D, L, U)
-            if sup is not False and self._fused_ok(z, params) and self._whole_flow():
+            if sup is not False and not self._padded_ok(z, params) and self._fused_ok(z, params) and self._whole_flow():
                 mean, alpha = self._bn_stats(_lib.require_device())  # ... or of the whole-flow coupling kernel
                 return ops.flow_log_prob_raw(z, params, mean, alpha, self.D, self.num_stages, self.num_layers,
                                              self.num_units, self.fusion, interval_consts=sup)[0]
@@ -432,6 +462,10 @@ class NormFlow(DensityEstimator):
         if self._ar_train_ok(z, params):
             masks, mean, alpha, D, L, U = self._ar_args()
             return ops.ar_flow_log_prob_train(z, params, masks, mean, alpha, None, D, L, U)
+        if self._padded_ok(z, params):
+            mean, alpha = self._bn_stats(_lib.require_device())
+            return ops.flow_padded_log_prob_raw(z, params, mean, alpha, self.D, self.num_stages, self.num_layers,
+                                                self.num_units)[0]
         if self._fused_ok(z, params):
             dev = _lib.require_device()
             mean, alpha = self._bn_stats(dev)

@@ -591,6 +591,69 @@ def flow_forward_raw(omega, params, bn_mean, bn_alpha, D, S, L, U, fusion=_lib.F
     return (z_out, sld, log_q) if want_log_q else (z_out, sld)
 
 
+def flow_padded_supported(D, S, L, U):
+    """tnf_flow_padded_supported: the whole-flow kernel in its padded layouts (2 <= D <= 63, D != 32)."""
+    return bool(lib.tnf_flow_padded_supported(D, S, L, U))
+
+
+def _padded_prep(z, params, bn_mean, bn_alpha):
+    _check3(z)
+    dev = _lib.require_device()
+    if z.dtype != torch.float32 or params.dtype != torch.float32:
+        raise TypeError("the fused flow kernels are float32")
+    zc = _stage(z, dev)  # rows of D floats; the kernel needs 4-byte alignment only, so a contiguous view is not copied
+    pc, pstride = _rows(params, dev)
+    return dev, zc, pc, pstride, _stats(bn_mean, dev), _stats(bn_alpha, dev)
+
+
+def flow_padded_log_prob_raw(z, params, bn_mean, bn_alpha, D, S, L, U, want_z0=False, want_sld=False, want_lp=True,
+                             count_reruns=False):
+    """tnf_flow_padded_log_prob_f32: flow_log_prob_raw on the padded whole-flow kernel (one launch, any
+    2 <= D <= 63 but 32).  Returns (log_prob | None, z0 | None, sum_log_det | None) (+ the rerun counter, see
+    flow_log_prob_raw)."""
+    home = z.device
+    dev, zc, pc, pstride, mean_c, alpha_c = _padded_prep(z, params, bn_mean, bn_alpha)
+    Mz, N = zc.shape[0], zc.shape[1]
+    Mp = pc.shape[0]
+    M = _bcast_M(Mz, Mp)
+    lp = torch.empty((M, N), dtype=torch.float32, device=dev) if want_lp else None
+    z0 = torch.empty((M, N, D), dtype=torch.float32, device=dev) if want_z0 else None
+    sld = torch.empty((M, N), dtype=torch.float32, device=dev) if want_sld else None
+    reruns = torch.zeros(1, dtype=torch.int32, device=dev) if count_reruns else None
+    if N > 0:
+        ws = _workspace(check(lib.tnf_flow_padded_workspace_bytes(M, N, D, S, L, U)), dev)
+        check(lib.tnf_flow_padded_log_prob_f32(zc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
+                                               None if lp is None else lp.data_ptr(),
+                                               None if z0 is None else z0.data_ptr(),
+                                               None if sld is None else sld.data_ptr(), Mz, Mp, N, D, S, L, U, pstride,
+                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr(),
+                                               None if reruns is None else reruns.data_ptr()))
+    out = tuple(t.to(home) if t is not None else None for t in (lp, z0, sld))
+    return out + (reruns,) if count_reruns else out
+
+
+def flow_padded_forward_raw(omega, params, bn_mean, bn_alpha, D, S, L, U, want_log_q=False):
+    """tnf_flow_padded_forward_f32: flow_forward_raw (frozen BatchNorm) on the padded whole-flow kernel.
+    Returns (z (M,N,D), sum_log_det (M,N)) and, with want_log_q, log_q (M,N) float64 = log N(omega) - sum_log_det
+    written by the kernel."""
+    home = omega.device
+    dev, oc, pc, pstride, mean_c, alpha_c = _padded_prep(omega, params, bn_mean, bn_alpha)
+    Mz, N = oc.shape[0], oc.shape[1]
+    Mp = pc.shape[0]
+    M = _bcast_M(Mz, Mp)
+    z_out = torch.empty((M, N, D), dtype=torch.float32, device=dev)
+    sld = torch.empty((M, N), dtype=torch.float32, device=dev)
+    log_q = torch.empty((M, N), dtype=torch.float64, device=dev) if want_log_q else None
+    if N > 0:
+        ws = _workspace(check(lib.tnf_flow_padded_workspace_bytes(M, N, D, S, L, U)), dev)
+        check(lib.tnf_flow_padded_forward_f32(oc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
+                                              z_out.data_ptr(), sld.data_ptr(), None if log_q is None else log_q.data_ptr(),
+                                              Mz, Mp, N, D, S, L, U, pstride, ws.data_ptr(), ws.numel(),
+                                              _lib.stream_ptr()))
+    out = tuple(t.to(home) if t is not None else None for t in (z_out, sld, log_q))
+    return out if want_log_q else out[:2]
+
+
 # ---------------------------------------------------------------------------
 # flow level, with autograd: log_prob through one fused kernel per layer, backward through one
 # MFMA backward kernel per layer (tnf_flow_log_prob_fwd_f32 / _bwd_f32)
