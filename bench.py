@@ -15,33 +15,34 @@ A "step" is one NormFlow.log_prob call over one (1, 2^20, 64) batch through the 
 with N GPUs every rank evaluates its own 2^20-sample batch (weak scaling) and `value` is
 the samples all ranks processed per second of the slowest rank.
 
-Timing protocol: every timed row is  settle (--settle-ms of the same call back to back: an MI355X that has been idle
+Timing protocol: the timed row is  settle (--settle-ms of the same call back to back: an MI355X that has been idle
 needs ~50 ms of load to reach the clock it holds)  ->  W warm-up steps  ->  barrier + synchronize ->
-K timed steps  ->  barrier + synchronize; `value` comes from that.  The contract's literal W + K steps on the idle GPU
-run first and are reported as `cold_start`.
+K timed steps  ->  barrier + synchronize; `value` comes from that.
 
-One JSON line is printed by rank 0.  Besides the contract's keys it carries
-  steady_state, cold_start -- the protocol above and the cold figure;
+A plain run does only that: it sets up, runs the timed row, writes --dump-outputs and prints one JSON line (rank 0)
+with the contract's keys, `config`, `steady_state`, `rccl_ranks` / `collective_backend` and
   roofline      -- the dominant kernel of the timed path, from HIP events recorded on the
-                   stream the kernels run on, inside the timed region;
+                   stream the kernels run on, inside the timed region.
+--full adds everything else the benchmark measures or checks, all of it outside the timed region:
+  cold_start    -- the contract's literal W + K steps on the GPU idle since set-up, run before the timed row;
   cpu_baseline  -- the PyTorch-CPU oracle (oracle/flow_oracle.py, verified equal to the
                    reference in the build container) timed on this box's host cores (os.cpu_count() threads;
                    `threads16` = the same at 16 threads);
   layer_chain   -- the same call with one fused kernel per coupling layer (k = 8, the
-                   HBM-bound design of north_star), measured after the timed region, with its own roofline;
+                   HBM-bound design of north_star), with its own roofline;
   sampling_layer_chain -- (1 GPU) the sampling direction, frozen statistics, one fused kernel per coupling layer;
   parity        -- max relative error of the GPU log_prob vs the oracle on 2^16 samples (ENFORCED: exit code 1
                    when it exceeds the tolerance);
-  rccl_ranks    -- sum over ranks of 1 through an RCCL all-reduce (proves N ranks took part);
   strong_scaling-- the same call with N = 2^20 samples IN TOTAL split over the ranks (north_star quotes both);
   train_step    -- BASELINE configs[3] per GPU: -mean(log_prob) on 2^19 samples, backward (reversible pair), Adam
-                   (with N GPUs: + the RCCL all-reduce of the flat gradient), outside the timed region; also with the
+                   (with N GPUs: + the RCCL all-reduce of the flat gradient); also with the
                    backward's overflow recovery off / by host read-back, and replayed as one HIP graph;
   configs       -- (1 GPU) BASELINE configs[1] (D = 32, own roofline) and configs[2] (ConditionalDensityEstimator,
                    (M, N) = (16, 2^16): frozen forward + log_prob);
   widened       -- (1 GPU) the SURVEY 8f rows: fused conditional flow, AR log_prob, the LFI step as a HIP graph,
                    sampling with fresh batch statistics under autograd.
---no-extras skips train_step, configs and widened (a clean per-kernel average under rocprofv3 --stats).
+With --full, --no-extras skips train_step, configs and widened (a clean per-kernel average under rocprofv3 --stats) and
+--no-cpu-baseline skips cpu_baseline and parity.
 --dump-outputs DIR writes the log_prob of the last timed step to DIR/log_prob.npy (rank 0; float32, 4 MB).  The inputs
 (z, parameters, BatchNorm statistics) are seeded and computed without the kernels under test, so the files of two builds
 can be compared element for element.
@@ -76,11 +77,15 @@ def parse_args():
     ap.add_argument("--settle-ms", type=float, default=150.0,
                     help="run the measured call back to back for this long before the W warm-up steps, so that the GPU has "
                          "reached the clock it holds under sustained load (it needs ~50 ms after an idle gap); 0 = off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline row, measure and check everything else: cold start, CPU baseline, "
+                         "per-layer chain, parity against the oracle, strong scaling, training step, configs and "
+                         "widened rows (off: the run does only what the headline figure needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
     ap.add_argument("--no-extras", action="store_true",
-                    help="headline path only: skip the training step, the configs rows and the widened rows (keeps a "
+                    help="with --full: skip the training step, the configs rows and the widened rows (keeps a "
                          "rocprofv3 --stats average of the headline kernel free of their smaller launches)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = os.cpu_count()")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="with --full: CPU baseline threads, 0 = os.cpu_count()")
     ap.add_argument("--dry-run-launcher", action="store_true",
                     help="print the command the self-launcher would run for --gpus N and exit (no GPU, no children)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -105,6 +110,8 @@ def launcher_command(args, port=None):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    if args.full:
+        cmd.append("--full")
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.no_extras:
@@ -334,9 +341,10 @@ def main():
 
     fused = bool(L_.lib.tnf_flow_fused_supported(D, S, L, U))
     main_fusion = L_.FUSE_FLOW if fused else L_.FUSE_LAYER
-    # the contract's literal W + K steps on a GPU that has just been idle (the model set-up above), for the record ...
-    wall_c, ev_c, _ = run(nf, z, main_fusion, args.steps, args.warmup, settle_ms=0.0)
-    wall_c = max_over_ranks(wall_c)
+    if args.full:
+        # the contract's literal W + K steps on a GPU that has just been idle (the model set-up above), for the record ...
+        wall_c, ev_c, _ = run(nf, z, main_fusion, args.steps, args.warmup, settle_ms=0.0)
+        wall_c = max_over_ranks(wall_c)
     # ... and the measurement proper: the same W + K steps once the clock has settled
     wall, ev, lp = run(nf, z, main_fusion, args.steps, args.warmup)
     wall_max = max_over_ranks(wall)
@@ -346,11 +354,12 @@ def main():
         np.save(os.path.join(args.dump_outputs, "log_prob.npy"), lp.detach().float().cpu().numpy())
 
     # the per-layer chain (k = 8), outside the timed region
-    wall_l, ev_l, lp_l = run(nf, z, L_.FUSE_LAYER, max(5, args.steps // 2), 2)
+    if args.full:
+        wall_l, ev_l, lp_l = run(nf, z, L_.FUSE_LAYER, max(5, args.steps // 2), 2)
 
     # strong scaling: 2^20 samples in total, split over the ranks (north_star: "N=2^20 ... at 1, 2, 4 and 8 GPUs")
     strong = None
-    if world > 1:
+    if args.full and world > 1:
         from torch_nf_amd.distributed import shard_bounds
 
         lo, hi = shard_bounds(N_PER_GPU, world, rank)
@@ -363,7 +372,7 @@ def main():
     # BASELINE configs[3], per-GPU share: one training step (loss = -mean log_prob, backward, Adam)
     # on 2^19 samples; outside the timed region.  With N GPUs the only collective is the gradient.
     train_ms = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         n_tr = 1 << 19
         p_train = nf.params.detach().clone().requires_grad_()
         nf_params_saved, nf.params = nf.params, p_train
@@ -463,7 +472,6 @@ def main():
     total_samples = N_PER_GPU * world * args.steps
     value = total_samples / wall_max / 1e6
     ev_mean = float(np.mean(ev))  # ms per call on the launch stream = the one kernel of the call (it builds its operands in its prologue)
-    roofline = None
     if fused:
         roofline = fused_roofline(D, ev_mean, N_PER_GPU, "flow_fused2_kernel<32,2,2,8,4>")
         roofline["note"] = ("achieved = algorithmic fp32 flops (42,176 per sample) / launch time; peak = dense f16 MFMA "
@@ -474,15 +482,8 @@ def main():
         # (6 x 16x16x32 + 18 x 16x16x16) = 15,360 flop/sample/layer, against 2.5 PFLOP/s dense f16
         roofline["issued_f16_mfma_tflops"] = round(N_PER_GPU * 15360 * 2 * S / (ev_mean * 1e-3) / 1e12, 1)
         roofline["f16_mfma_peak_tflops"] = F16_MFMA_TFLOPS
-    evl_mean = float(np.mean(ev_l))
-    layer_chain = {
-        "value": round(N_PER_GPU / (evl_mean * 1e-3) / 1e6, 2), "unit": "M samples/s", "launches": 2 * S,
-        "ms_per_step": round(evl_mean, 4),
-        "target_60pct_of_hbm_roof": round(0.6 * HBM_PEAK_GBS * 1e9 / bytes_per_sample_chain(D, 2 * S) / 1e6, 1),
-        "roofline": chain_roofline(D, evl_mean, N_PER_GPU, "flow_range2_kernel<32,2,2,8,*,*,0> (one coupling layer per launch)"),
-    }
-    if roofline is None:
-        roofline = layer_chain["roofline"]
+    else:  # the timed path is the per-layer chain itself
+        roofline = chain_roofline(D, ev_mean, N_PER_GPU, "flow_range2_kernel<32,2,2,8,*,*,0> (one coupling layer per launch)")
 
     out = {
         "metric": "M samples/sec NormFlow.log_prob, D=64 RealNVPx8, N=2^20",
@@ -508,26 +509,34 @@ def main():
                          "what": "every timed row is preceded by settle_ms of the same call back to back, then its W warm-up "
                                  "steps: after an idle gap the GPU needs ~50 ms of sustained load to reach the clock it holds "
                                  "(whole-flow kernel: 0.278 ms per launch at first, 0.220 ms from the 200th on)"},
-        "cold_start": {"value": round(N_PER_GPU * world * args.steps / wall_c / 1e6, 2), "unit": "M samples/s",
-                       "ms_per_step": round(wall_c / args.steps * 1e3, 4), "launch_ms": round(float(np.mean(ev_c)), 4),
-                       "what": "the same W warm-up + K timed steps without the settle phase, on a GPU idle since set-up"},
-        "rccl_ranks": rccl_ranks,
-        "collective_backend": None if world == 1 else ("gloo, all ranks on cuda:0 (REHEARSAL, not a measurement)" if rehearse
-                                                       else "nccl (RCCL)"),
-        "roofline": roofline,
-        "layer_chain": layer_chain,
-        "strong_scaling": strong,
-        "train_step": None if train_ms is None else {
+    }
+    if args.full:
+        out["cold_start"] = {"value": round(N_PER_GPU * world * args.steps / wall_c / 1e6, 2), "unit": "M samples/s",
+                             "ms_per_step": round(wall_c / args.steps * 1e3, 4), "launch_ms": round(float(np.mean(ev_c)), 4),
+                             "what": "the same W warm-up + K timed steps without the settle phase, on a GPU idle since set-up"}
+    out["rccl_ranks"] = rccl_ranks
+    out["collective_backend"] = None if world == 1 else ("gloo, all ranks on cuda:0 (REHEARSAL, not a measurement)" if rehearse
+                                                         else "nccl (RCCL)")
+    out["roofline"] = roofline
+    if args.full:
+        evl_mean = float(np.mean(ev_l))
+        out["layer_chain"] = {
+            "value": round(N_PER_GPU / (evl_mean * 1e-3) / 1e6, 2), "unit": "M samples/s", "launches": 2 * S,
+            "ms_per_step": round(evl_mean, 4),
+            "target_60pct_of_hbm_roof": round(0.6 * HBM_PEAK_GBS * 1e9 / bytes_per_sample_chain(D, 2 * S) / 1e6, 1),
+            "roofline": chain_roofline(D, evl_mean, N_PER_GPU, "flow_range2_kernel<32,2,2,8,*,*,0> (one coupling layer per launch)"),
+        }
+        out["strong_scaling"] = strong
+        out["train_step"] = None if train_ms is None else {
             "ms": round(train_ms, 3), "samples_per_gpu": 1 << 19,
             "overflow_recovery": "device-gated fp32 recomputation (default)",
             "ms_recovery_off": round(train_ms_off, 3), "ms_recovery_by_host_readback": round(train_ms_host, 3),
             "ms_as_one_hip_graph": train_ms_graph if not isinstance(train_ms_graph, float) else round(train_ms_graph, 3),
             "value": round((1 << 19) * world / (train_ms * 1e-3) / 1e6, 1), "unit": "M samples/s",
             "what": "loss = -mean(log_prob): whole-flow forward keeping z0, one-kernel reversible backward (split-f16 MFMA); "
-                    + ("RCCL all-reduce of the flat gradient (81,856 B, one bucket); " if world > 1 else "") + "Adam step"},
-    }
+                    + ("RCCL all-reduce of the flat gradient (81,856 B, one bucket); " if world > 1 else "") + "Adam step"}
 
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         from tools import bench_rows
 
         cfg = {}
@@ -573,7 +582,7 @@ def main():
         out["widened"] = bench_rows.widened_rows(tnf)
 
     parity_ok = True
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         threads = args.cpu_threads or (os.cpu_count() or 1)
         base, orc, params, stats = cpu_baseline(nf, threads, D, S, L, U)
         out["cpu_baseline"] = base

@@ -399,3 +399,18 @@ def test_bench_launcher_dry_run():
     assert cmd[cmd.index("--nproc-per-node") + 1] == "8" and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     tail = cmd[cmd.index(os.path.join(ROOT, "bench.py")):]
     assert tail[1:] == ["--gpus", "8", "--steps", "7", "--warmup", "2"]
+
+
+def test_bench_launcher_dry_run_forwards_full():
+    """--full and the options that only act with it reach every rank of the self-launched group."""
+    import json
+    import subprocess
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "2",
+                          "--full", "--no-cpu-baseline", "--no-extras", "--dry-run-launcher"],
+                         capture_output=True, text=True, env=env, timeout=120)
+    assert res.returncode == 0, res.stderr
+    cmd = json.loads(res.stdout.strip().splitlines()[-1])["launcher"]
+    tail = cmd[cmd.index(os.path.join(ROOT, "bench.py")):]
+    assert tail[1:] == ["--gpus", "2", "--steps", "7", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras"]

@@ -1,5 +1,5 @@
-"""Rows of bench.py's JSON line that sit outside the timed headline region: BASELINE configs[2] and the single-GPU
-extras for the SURVEY 8f rows.  (The CPU baseline -- the only leg that may touch oracle/ -- lives in bench.py itself.)"""
+"""Rows that bench.py --full adds to its JSON line, outside the timed headline region: BASELINE configs[2] and the
+single-GPU extras for the SURVEY 8f rows.  (The CPU baseline -- the only leg that may touch oracle/ -- lives in bench.py itself.)"""
 import time
 
 import numpy as np
