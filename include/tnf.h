@@ -581,6 +581,46 @@ int tnf_flow_padded_forward_f32(const float* omega, const float* params, const f
                                 int32_t D, int32_t num_stages, int32_t num_layers, int32_t num_units,
                                 int64_t params_row_stride, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- exponential families of an EFN objective (exponential_families.py:104-307) ----------------------------
+ * family TNF_EF_MVN:       T(z) = [z | z_i z_j for i <= j, row-major over the upper triangle, i.e. in the order of
+ *                          np.triu_indices(D)] (:140-156), D_eta = D + D(D+1)/2 (:108-114)
+ * family TNF_EF_DIRICHLET: T(z) = [log(z + 1e-10) | sum_i log(z_i + 1e-10)] (:253-270), D_eta = D + 1 (:222-229);
+ *                          the epsilon is added in the tensor's own dtype, as torch does.
+ * tnf_ef_num_eta: D_eta, or -1 for an unknown family or D outside 1 .. TNF_EF_MAX_D.
+ * tnf_ef_suffstats: z (rows, D) -> T_out (rows, D_eta), float32 or float64, any supported D; each MVN product is one
+ * correctly rounded multiply.  tnf_ef_suffstats_backward: g_z (rows, D) from g_T (rows, D_eta), recomputed from z. */
+enum { TNF_EF_MVN = 0, TNF_EF_DIRICHLET = 1 };
+#define TNF_EF_MAX_D 32768
+int32_t tnf_ef_num_eta(int32_t family, int32_t D);
+int tnf_ef_suffstats(int32_t dtype, int32_t family, const void* z, void* T_out, int64_t rows, int32_t D, void* stream);
+int tnf_ef_suffstats_backward(int32_t dtype, int32_t family, const void* z, const void* g_T, void* g_z, int64_t rows,
+                              int32_t D, void* stream);
+/* The EFN loss term without T(z): out[m][n] = eta[m] . T(z[m][n]), which the reference forms as
+ * torch.matmul(T(z), eta[:, :, None]) over a materialised (M, N, D_eta) tensor (notebooks/two_network_arch.ipynb,
+ * EFNLoss).  z (M, N, D), eta (M, >= D_eta) with ld_eta elements per row, out (M, N), all of `dtype`.
+ * tnf_ef_dot_supported: 1 where the fused float32 kernel exists (both families, 1 <= D <= 64), else 0; every other
+ * float32 shape and all of float64 run a shape-generic kernel (one sample per lane) -- never a composition of other
+ * entry points.  TNF_OPT_FORCE_GENERIC selects the generic kernel for a fused shape too.
+ * tnf_ef_dot_backward: from g_out (M, N), g_z (M, N, D) = g_out * d out / d z and g_eta (M, D_eta), contiguous,
+ * = sum_n g_out[m][n] T(z[m][n]).  Either may be NULL and is then skipped.  g_eta is bit-reproducible: fixed-order
+ * partial rows in the workspace, then an ordered sum; no float atomics.  The workspace is used for g_eta only:
+ * tnf_ef_dot_bwd_workspace_bytes = M * G * D_eta * 8 with G = min(ceil(N / R), max(1, 256 / M)) partial rows per
+ * context, R <= 64 samples per staged tile (2.2 MB for one context at D = 64, 1.9 MB for 1024 contexts at D = 20);
+ * -1 on bad arguments or D > 6143 (a tile row no longer fits the LDS).
+ * tnf_ef_launch_count: launches of the FUSED kernels this process has enqueued, counted like tnf_diag_launch_count's
+ * families but in a space of their own (the flow families above are a closed, pinned set): TNF_EF_COUNT_DOT
+ * (ef_dot_mvn_kernel<D> / ef_dot_dirichlet_kernel) and TNF_EF_COUNT_DOT_BWD (their g_z kernels); -1 for another id.
+ * A test reads them around a call to prove the fused kernel, not the generic one or a composition, served it. */
+enum { TNF_EF_COUNT_DOT = 0, TNF_EF_COUNT_DOT_BWD = 1, TNF_EF_COUNTERS = 2 };
+int64_t tnf_ef_launch_count(int32_t which);
+int tnf_ef_dot_supported(int32_t family, int32_t D);
+int tnf_ef_dot(int32_t dtype, int32_t family, const void* z, const void* eta, void* out, int64_t M, int64_t N,
+               int32_t D, int64_t ld_eta, void* stream);
+int64_t tnf_ef_dot_bwd_workspace_bytes(int32_t family, int64_t M, int64_t N, int32_t D);
+int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void* eta, const void* g_out, void* g_z,
+                        void* g_eta, int64_t M, int64_t N, int32_t D, int64_t ld_eta, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

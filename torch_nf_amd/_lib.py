@@ -26,6 +26,8 @@ DIAG_FLOW_FUSED2, DIAG_FLOW_FUSED2_FWD, DIAG_FLOW_FUSED3, DIAG_FLOW_F16, DIAG_FL
 DIAG_FLOW_RANGE2, DIAG_FLOW_RANGE2_FWD, DIAG_COUPLING_MFMA, DIAG_COND_FLOW = 12, 13, 14, 15
 DIAG_FLOW_PADDED, DIAG_FLOW_PADDED_FWD = 16, 17
 DIAG_FAMILIES = 18
+EF_MVN, EF_DIRICHLET = 0, 1
+EF_COUNT_DOT, EF_COUNT_DOT_BWD = 0, 1  # tnf_ef_launch_count
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
@@ -141,6 +143,14 @@ SIGNATURES = {
                                                     _i32, _i32, _i64, _vp, _i64, _vp, _vp]),
     "tnf_flow_padded_forward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
                                                    _i32, _i32, _i64, _vp, _i64, _vp]),
+    "tnf_ef_num_eta": (_i32, [_i32, _i32]),
+    "tnf_ef_suffstats": (ctypes.c_int, [_i32, _i32, _vp, _vp, _i64, _i32, _vp]),
+    "tnf_ef_suffstats_backward": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "tnf_ef_launch_count": (_i64, [_i32]),
+    "tnf_ef_dot_supported": (ctypes.c_int, [_i32, _i32]),
+    "tnf_ef_dot": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _vp]),
+    "tnf_ef_dot_bwd_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32]),
+    "tnf_ef_dot_backward": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _vp, _i64, _vp]),
 }
 
 

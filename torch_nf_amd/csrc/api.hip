@@ -17,6 +17,11 @@ void diag_count(int family) {
     if (family >= 0 && family < TNF_DIAG_FAMILIES) g_diag_launches[family].fetch_add(1, std::memory_order_relaxed);
 }
 
+static std::atomic<long long> g_ef_launches[TNF_EF_COUNTERS];
+void ef_count(int which) {
+    if (which >= 0 && which < TNF_EF_COUNTERS) g_ef_launches[which].fetch_add(1, std::memory_order_relaxed);
+}
+
 char* err_buf() {
     static thread_local char buf[512] = {0};
     return buf;
@@ -780,6 +785,86 @@ int tnf_to_simplex_backward(int32_t dtype, const void* z, const void* g_z_out, c
     if (rows == 0) return TNF_OK;
     if (!z || !g_z_out || !g_log_det || !g_z) return fail(TNF_EINVAL, "tnf_to_simplex_backward: NULL pointer");
     return launch_to_simplex_backward(dtype, z, g_z_out, g_log_det, g_z, rows, D_in, D_attr, as_stream(stream));
+}
+
+// ---- exponential families (expfam_kernels.hip) ----
+static int ef_check(const char* fn, int32_t dtype, int32_t family, int32_t D) {
+    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "%s: dtype %d", fn, dtype);
+    if (family != TNF_EF_MVN && family != TNF_EF_DIRICHLET) return fail(TNF_EINVAL, "%s: family %d", fn, family);
+    if (D < 1) return fail(TNF_EINVAL, "%s: D=%d must be positive", fn, D);
+    if (D > TNF_EF_MAX_D) return fail(TNF_EUNSUPPORTED, "%s: D=%d exceeds %d", fn, D, TNF_EF_MAX_D);
+    return TNF_OK;
+}
+
+int32_t tnf_ef_num_eta(int32_t family, int32_t D) {
+    const int64_t n = ef_num_eta(family, D);
+    if (n < 0) return fail(TNF_EINVAL, "tnf_ef_num_eta: family=%d D=%d", family, D);
+    return (int32_t)n;
+}
+
+int tnf_ef_suffstats(int32_t dtype, int32_t family, const void* z, void* T_out, int64_t rows, int32_t D, void* stream) {
+    const int rc = ef_check("tnf_ef_suffstats", dtype, family, D);
+    if (rc) return rc;
+    if (rows < 0) return fail(TNF_EINVAL, "tnf_ef_suffstats: rows=%lld", (long long)rows);
+    if (rows > 0 && (!z || !T_out)) return fail(TNF_EINVAL, "tnf_ef_suffstats: NULL pointer");
+    return launch_ef_suffstats(dtype, family, z, T_out, rows, D, as_stream(stream));
+}
+
+int tnf_ef_suffstats_backward(int32_t dtype, int32_t family, const void* z, const void* g_T, void* g_z, int64_t rows,
+                              int32_t D, void* stream) {
+    const int rc = ef_check("tnf_ef_suffstats_backward", dtype, family, D);
+    if (rc) return rc;
+    if (rows < 0) return fail(TNF_EINVAL, "tnf_ef_suffstats_backward: rows=%lld", (long long)rows);
+    if (rows > 0 && (!z || !g_T || !g_z)) return fail(TNF_EINVAL, "tnf_ef_suffstats_backward: NULL pointer");
+    return launch_ef_suffstats_backward(dtype, family, z, g_T, g_z, rows, D, as_stream(stream));
+}
+
+int64_t tnf_ef_launch_count(int32_t which) {
+    if (which < 0 || which >= TNF_EF_COUNTERS) return fail(TNF_EINVAL, "tnf_ef_launch_count: counter %d", which);
+    return g_ef_launches[which].load(std::memory_order_relaxed);
+}
+
+int tnf_ef_dot_supported(int32_t family, int32_t D) { return ef_dot_fused_supported(family, D) ? 1 : 0; }
+
+static int ef_check_dot(const char* fn, int32_t dtype, int32_t family, int64_t M, int64_t N, int32_t D, int64_t ld_eta) {
+    const int rc = ef_check(fn, dtype, family, D);
+    if (rc) return rc;
+    if (M < 0 || N < 0) return fail(TNF_EINVAL, "%s: bad batch sizes M=%lld N=%lld", fn, (long long)M, (long long)N);
+    if (ld_eta < ef_num_eta(family, D))
+        return fail(TNF_EINVAL, "%s: ld_eta=%lld is shorter than D_eta=%lld", fn, (long long)ld_eta,
+                    (long long)ef_num_eta(family, D));
+    return TNF_OK;
+}
+
+int tnf_ef_dot(int32_t dtype, int32_t family, const void* z, const void* eta, void* out, int64_t M, int64_t N,
+               int32_t D, int64_t ld_eta, void* stream) {
+    const int rc = ef_check_dot("tnf_ef_dot", dtype, family, M, N, D, ld_eta);
+    if (rc) return rc;
+    if (M * N > 0 && (!z || !eta || !out)) return fail(TNF_EINVAL, "tnf_ef_dot: NULL pointer");
+    return launch_ef_dot(dtype, family, z, eta, out, M, N, D, ld_eta, as_stream(stream));
+}
+
+int64_t tnf_ef_dot_bwd_workspace_bytes(int32_t family, int64_t M, int64_t N, int32_t D) {
+    if (M < 0 || N < 0) return fail(TNF_EINVAL, "tnf_ef_dot_bwd_workspace_bytes: M=%lld N=%lld", (long long)M, (long long)N);
+    const int64_t b = ef_dot_bwd_workspace(family, M < 1 ? 1 : M, N, D);
+    if (b < 0) return fail(TNF_EINVAL, "tnf_ef_dot_bwd_workspace_bytes: family=%d D=%d", family, D);
+    return b;
+}
+
+int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void* eta, const void* g_out, void* g_z,
+                        void* g_eta, int64_t M, int64_t N, int32_t D, int64_t ld_eta, void* workspace,
+                        int64_t workspace_bytes, void* stream) {
+    const char* fn = "tnf_ef_dot_backward";
+    const int rc = ef_check_dot(fn, dtype, family, M, N, D, ld_eta);
+    if (rc) return rc;
+    if (M * N > 0 && (!z || !eta || !g_out)) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
+    if (g_eta && M > 0) {
+        const int64_t need = ef_dot_bwd_workspace(family, M, N, D);
+        if (need < 0) return fail(TNF_EUNSUPPORTED, "%s: no g_eta kernel for D=%d", fn, D);
+        if (!workspace || workspace_bytes < need)
+            return fail(TNF_EWORKSPACE, "%s: workspace %lld B < %lld B", fn, (long long)workspace_bytes, (long long)need);
+    }
+    return launch_ef_dot_backward(dtype, family, z, eta, g_out, g_z, g_eta, M, N, D, ld_eta, workspace, as_stream(stream));
 }
 
 int tnf_base_log_density_f64(int32_t dtype, const void* omega, double* out, int64_t rows, int32_t D,

@@ -319,6 +319,18 @@ int launch_to_simplex(int dtype, const void* z, void* z_out, void* log_det, int6
                       hipStream_t st);
 int launch_to_simplex_backward(int dtype, const void* z, const void* g_zout, const void* g_ld, void* g_z, int64_t rows,
                                int Din, int Dc, hipStream_t st);
+// exponential families (expfam_kernels.hip): T(z), eta . T(z) and their backward passes
+int64_t ef_num_eta(int family, int D);  // -1: unknown family or D outside 1 .. TNF_EF_MAX_D
+bool ef_dot_fused_supported(int family, int D);
+void ef_count(int which);  // api.hip: launch counters behind tnf_ef_launch_count
+int64_t ef_dot_bwd_workspace(int family, int64_t M, int64_t N, int D);
+int launch_ef_suffstats(int dtype, int family, const void* z, void* out, int64_t rows, int D, hipStream_t st);
+int launch_ef_suffstats_backward(int dtype, int family, const void* z, const void* g_T, void* g_z, int64_t rows, int D,
+                                 hipStream_t st);
+int launch_ef_dot(int dtype, int family, const void* z, const void* eta, void* out, int64_t M, int64_t N, int D,
+                  int64_t ld_eta, hipStream_t st);
+int launch_ef_dot_backward(int dtype, int family, const void* z, const void* eta, const void* g_out, void* g_z,
+                           void* g_eta, int64_t M, int64_t N, int D, int64_t ld_eta, void* ws, hipStream_t st);
 // MAF on the matrix pipe (maf_mfma.hip): float32, D <= 64, U <= 64, L <= 5
 struct MafArgs {
     const float* z;

@@ -1181,6 +1181,124 @@ def to_simplex(z, D_attr):
 
 
 # ---------------------------------------------------------------------------
+# Exponential families of an EFN objective: sufficient statistics T(z) and the contraction eta . T(z)
+# ---------------------------------------------------------------------------
+def ef_num_eta(family, D):
+    n = lib.tnf_ef_num_eta(family, D)
+    if n < 0:
+        raise ValueError("no exponential family %r with D=%r" % (family, D))
+    return n
+
+
+def ef_suffstats_raw(z, family):
+    """tnf_ef_suffstats: (M, N, D) -> T(z) (M, N, D_eta), on z's device."""
+    _check3(z)
+    dev = _lib.require_device()
+    home = z.device
+    code = _dtype_code(z)
+    zc = _stage(z, dev)
+    M, N, D = zc.shape
+    out = torch.empty((M, N, ef_num_eta(family, D)), dtype=z.dtype, device=dev)
+    check(lib.tnf_ef_suffstats(code, family, zc.data_ptr(), out.data_ptr(), M * N, D, _lib.stream_ptr()))
+    return out if home == dev else out.to(home)
+
+
+class _EfSuffstatsFn(torch.autograd.Function):
+    @_records_options
+    def forward(ctx, z, family):
+        out = ef_suffstats_raw(z, family)
+        ctx.save_for_backward(z)
+        ctx.family = family
+        return out
+
+    @_reenters_options
+    def backward(ctx, g_T):
+        (z,) = ctx.saved_tensors
+        dev = _lib.require_device()
+        zc = _stage(z.detach(), dev)
+        M, N, D = zc.shape
+        g = _grad_or_zeros(g_T, (M, N, ef_num_eta(ctx.family, D)), z.dtype, dev)
+        gz = torch.empty_like(zc)
+        check(lib.tnf_ef_suffstats_backward(_dtype_code(z), ctx.family, zc.data_ptr(), g.data_ptr(), gz.data_ptr(), M * N,
+                                            D, _lib.stream_ptr()))
+        return (gz if z.device == dev else gz.to(z.device)), None
+
+
+def ef_suffstats(z, family):
+    if torch.is_grad_enabled() and z.requires_grad:
+        return _EfSuffstatsFn.apply(z, family)
+    return ef_suffstats_raw(z, family)
+
+
+def _ef_dot_check(z, eta, family):
+    _check3(z)
+    if eta.dim() != 2:
+        raise ValueError("eta must be (M, D_eta), got shape %s" % (tuple(eta.shape),))
+    M, N, D = z.shape
+    if eta.shape[0] != M:
+        raise RuntimeError("batch dimensions of z (%d) and eta (%d) do not match" % (M, eta.shape[0]))
+    if eta.shape[1] != ef_num_eta(family, D):
+        raise ValueError("eta has %d columns, the family's D_eta is %d" % (eta.shape[1], ef_num_eta(family, D)))
+    if eta.dtype != z.dtype:
+        raise TypeError("eta (%s) and z (%s) must have one dtype" % (eta.dtype, z.dtype))
+
+
+def ef_dot_raw(z, eta, family):
+    """tnf_ef_dot: out[m, n] = eta[m] . T(z[m, n]) without forming T(z).  Returns (M, N) on z's device."""
+    _ef_dot_check(z, eta, family)
+    dev = _lib.require_device()
+    home = z.device
+    code = _dtype_code(z)
+    zc = _stage(z, dev)
+    ec, ld_eta = _rows(eta, dev)
+    M, N, D = zc.shape
+    out = torch.empty((M, N), dtype=z.dtype, device=dev)
+    check(lib.tnf_ef_dot(code, family, zc.data_ptr(), ec.data_ptr(), out.data_ptr(), M, N, D, ld_eta, _lib.stream_ptr()))
+    return out if home == dev else out.to(home)
+
+
+class _EfDotFn(torch.autograd.Function):
+    @_records_options
+    def forward(ctx, z, eta, family):
+        out = ef_dot_raw(z, eta, family)
+        ctx.save_for_backward(z, eta)
+        ctx.family = family
+        return out
+
+    @_reenters_options
+    def backward(ctx, g_out):
+        z, eta = ctx.saved_tensors
+        dev = _lib.require_device()
+        zc = _stage(z.detach(), dev)
+        ec, ld_eta = _rows(eta.detach(), dev)
+        M, N, D = zc.shape
+        g = _grad_or_zeros(g_out, (M, N), z.dtype, dev)
+        want_z, want_eta = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gz = torch.empty_like(zc) if want_z else None
+        ge = torch.empty((M, eta.shape[1]), dtype=z.dtype, device=dev) if want_eta else None
+        ws, need = None, 0
+        if want_eta:
+            need = lib.tnf_ef_dot_bwd_workspace_bytes(ctx.family, M, N, D)
+            check(need)
+            ws = _workspace(need, dev)
+        check(lib.tnf_ef_dot_backward(_dtype_code(z), ctx.family, zc.data_ptr(), ec.data_ptr(), g.data_ptr(),
+                                      gz.data_ptr() if want_z else None, ge.data_ptr() if want_eta else None, M, N, D,
+                                      ld_eta, ws.data_ptr() if want_eta else None, ws.numel() if want_eta else 0,
+                                      _lib.stream_ptr()))
+        if want_z and z.device != dev:
+            gz = gz.to(z.device)
+        if want_eta and eta.device != dev:
+            ge = ge.to(eta.device)
+        return gz, ge, None
+
+
+def ef_dot(z, eta, family):
+    if torch.is_grad_enabled() and (z.requires_grad or eta.requires_grad):
+        return _EfDotFn.apply(z, eta, family)
+    return ef_dot_raw(z, eta, family)
+
+
+# ---------------------------------------------------------------------------
 # Conditional flow with one sample per context: param_net's last Linear fused into the flow
 # ---------------------------------------------------------------------------
 def _cond_width(H):
