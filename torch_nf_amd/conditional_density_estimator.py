@@ -164,20 +164,24 @@ class ConditionalDensityEstimator(torch.nn.Module):
         home = next(self.param_net.parameters()).device  # where NormFlow would return them: the parameters' device
         return (z if z.device == home else z.to(home)), (log_q if log_q.device == home else log_q.to(home))
 
+    def _fusable(self, x):
+        """What both fused conditioner kernels need: the switch, a coupling flow without support layer on constant
+        statistics (bijectors.py:414-415 keeps their graph; the kernels treat them as constants), float32, a shape the
+        kernel covers."""
+        nf = self.density_estimator
+        last = self.param_net[-1]
+        return (self.fuse_conditioner and nf.arch_type == "coupling" and nf.support_layer is None
+                and not nf._stats_in_graph() and x.dtype == torch.float32 and last.weight.dtype == torch.float32
+                and ops.cond_flow_supported(nf.D, nf.num_stages, nf.num_layers, nf.num_units, last.in_features))
+
     def _fused_sampling_ok(self, x):
         """cde(x, N = 1) with frozen statistics on a coupling flow, outside autograd (the samples' gradient with respect
         to the context network goes through the materialised path)."""
-        nf = self.density_estimator
-        last = self.param_net[-1]
-        if not (self.fuse_conditioner and x.dim() == 2 and x.size(0) >= self.fuse_min_contexts):
-            return False
-        if nf.arch_type != "coupling" or nf.support_layer is not None or nf._stats_in_graph():
+        if not (x.dim() == 2 and x.size(0) >= self.fuse_min_contexts):
             return False
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.param_net.parameters())):
             return False
-        if x.dtype != torch.float32 or last.weight.dtype != torch.float32:
-            return False
-        return ops.cond_flow_supported(nf.D, nf.num_stages, nf.num_layers, nf.num_units, last.in_features)
+        return self._fusable(x)
 
     def _fused_sampling(self, x, omega):
         """omega (M, 1, D) float32 on the device -> (z (M, 1, D), sum_log_det (M, 1))."""
@@ -196,18 +200,9 @@ class ConditionalDensityEstimator(torch.nn.Module):
         """One sample per context (the SNPE layout z[:, None, :]) on a coupling flow: the last Linear
         of param_net runs inside the flow kernel (tnf_cond_flow_log_prob_f32) and the (M, D_params)
         parameter tensor is never materialised."""
-        nf = self.density_estimator
-        last = self.param_net[-1]
-        if not (self.fuse_conditioner and z.dim() == 3 and z.size(1) == 1 and x.dim() == 2
-                and z.size(0) == x.size(0) and z.size(0) >= self.fuse_min_contexts):
-            return False
-        if nf.arch_type != "coupling" or nf.support_layer is not None or z.size(2) != nf.D:
-            return False
-        if nf._stats_in_graph():
-            return False  # the fused kernels treat the statistics as constants (bijectors.py:414-415 keeps their graph)
-        if z.dtype != torch.float32 or x.dtype != torch.float32 or last.weight.dtype != torch.float32:
-            return False
-        return ops.cond_flow_supported(nf.D, nf.num_stages, nf.num_layers, nf.num_units, last.in_features)
+        return (z.dim() == 3 and z.size(1) == 1 and x.dim() == 2 and z.size(0) == x.size(0)
+                and z.size(0) >= self.fuse_min_contexts and z.size(2) == self.density_estimator.D
+                and z.dtype == torch.float32 and self._fusable(x))
 
     def log_prob(self, z, x):
         """conditional_density_estimator.py:101-104."""

@@ -6,19 +6,55 @@ bijector stack, flat-parameter slicing, `__call__(N, params, freeze_bn)`,
 `forward`, `inverse_and_log_det`, `log_prob`, `count_num_params`, `D_params`,
 `params`, `bijectors`.
 
-Execution:
-  * arch_type="coupling", float32, no autograd, a shape with an MFMA kernel
-    (tnf_has_fast_path): ONE call of tnf_flow_log_prob_f32 / tnf_flow_forward_f32
-    (whole flow in one kernel, or one kernel per coupling layer).
-  * anything else: the reference's bijector loop, each bijector one HIP kernel.
-arch_type "AR" (MAF) composes per bijector.  A support layer (ToInterval / ToSimplex) is one
-extra elementwise kernel after the stack in `forward` and before it in `log_prob`.
+Execution: `NormFlow._route` names the kernel family of every call; each public operation stages its inputs, asks it
+once and runs that one arm.  First match wins, top to bottom.  "plain" = z and params float32 and, with grad mode on,
+neither requires grad; "const stats" = the cached BatchNorm statistics carry no graph (`_stats_in_graph()` is False:
+only the per-bijector composition differentiates through them); "not few" = not (several parameter rows and fewer than
+32 samples each); "3-d" = z is (M, N, D).
+
+  family            offered to           conditions                                                  ops entry
+  ----------------  -------------------  ----------------------------------------------------------  --------------------
+  batch_chain       forward, fresh       fused's conditions, fused_batch_forward, one parameter row  flow_forward_batch_raw
+                    statistics           per z row, flow_train_supported at N = 32, and M*N > 1 or
+                                         batch_stats_reduce set
+  batch_train       forward, fresh       coupling, float32, batch_stats_reduce unset, the chain's    flow_forward_train
+                    statistics           shape conditions, M*N >= 32 (one autograd node)
+  ar_fused          forward (frozen),    AR, plain, const stats, 3-d, ar_flow_supported; forward:    ar_flow_forward_raw,
+                    log_prob, inverse    support layer absent or ToInterval                          ar_flow_log_prob_raw
+  ar_train          log_prob             AR, fused_ar_training, grad mode on, const stats, float32,  ar_flow_log_prob_train
+                                         params requires grad and z does not, 3-d, M_z >= M_p,
+                                         ar_flow_supported, ar_flow_train_supported
+  padded            forward (frozen),    coupling, plain, const stats, not few, 3-d, fusion AUTO or  flow_padded_forward_raw,
+                    log_prob, inverse    FLOW, flow_padded_supported                                 flow_padded_log_prob_raw
+  fused             forward (frozen),    coupling, plain, const stats, not few, has_fast_path        flow_forward_raw,
+                    log_prob, inverse    (`_fused_ok`; whole flow or per-layer chain as `fusion`     flow_log_prob_raw
+                                         resolves)
+  train_reversible  log_prob             coupling, float32, const stats, 3-d, M_z >= M_p,            flow_log_prob_train
+                                         reversible_training, flow_train_rev_supported               (reversible=True)
+  train_layers      log_prob             the same, flow_train_supported                              (reversible=False)
+  bijectors         all                  everything else: the reference's loop, one kernel per       coupling, maf, affine,
+                                         bijector                                                    bn_apply, bn_batch_forward
+
+Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
+a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded` and the per-layer chain do not.
+Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
+`inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
+Sampling: the base density is evaluated first (base_log_density_f64), except that `padded` and the whole-flow `fused`
+kernel write log_q themselves for a float32 tensor draw (`Route.writes_log_q`).
 """
+import collections
+
 import numpy as np
 import torch
 
 from . import _lib, ops
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
+
+
+# a call's route: the kernel family, whether that kernel evaluates the support layer itself, and (sampling) whether it
+# writes log_q itself
+Route = collections.namedtuple("Route", "family fuse_support writes_log_q")
+_BIJECTORS, _FUSED = Route("bijectors", False, False), Route("fused", False, False)  # the two commonest, built once
 
 
 def _min_two(val):
@@ -176,18 +212,43 @@ class NormFlow(DensityEstimator):
             self.__dict__["_bn_cache"] = cached
         return cached[1], cached[2]
 
-    def _ar_fused_ok(self, z, params):
+    def _facts(self, z, params):
+        """What several families ask of a call, computed once, as the plain tuple (arch_type, (D, S, L, U),
+        stats_graph, f32, plain, inference): the configuration (every read of it runs a validating descriptor); the
+        statistics carry a graph; z and params are float32; the call is plain (float32 and nothing requires grad); it
+        is inference for the one-call coupling kernels (a coupling stack, plain, constant statistics, and not
+        per-context weights with fewer than 32 samples each -- the SNPE layout, N = 1, whose prepared operand images,
+        ~100 KB per context, would outweigh the samples).  A tuple, not a class: this runs on every call."""
+        arch, grad = self.arch_type, torch.is_grad_enabled()
+        stats_graph = grad and self._stats_in_graph()
+        f32 = z.dtype == torch.float32 and params.dtype == torch.float32
+        plain = f32 and not (grad and (z.requires_grad or params.requires_grad))
+        inference = (arch == "coupling" and plain and not stats_graph
+                     and not (params.size(0) > 1 and z.size(1) < 32))
+        return arch, (self.D, self.num_stages, self.num_layers, self.num_units), stats_graph, f32, plain, inference
+
+    def _ar_fused_ok(self, z, params, facts=None):
         """[MAF, BatchNorm, Affine] as one kernel: float32, no autograd, shape covered by the MFMA MAF kernel."""
-        if self.arch_type != "AR" or z.dtype != torch.float32 or params.dtype != torch.float32:
-            return False
-        if torch.is_grad_enabled() and (z.requires_grad or params.requires_grad or self._stats_in_graph()):
-            return False
-        return z.dim() == 3 and ops.ar_flow_supported(self.D, self.num_layers, self.num_units)
+        arch, (D, _, L, U), stats_graph, _, plain, _ = facts or self._facts(z, params)
+        return arch == "AR" and plain and not stats_graph and z.dim() == 3 and ops.ar_flow_supported(D, L, U)
+
+    def _ar_train_ok(self, z, params, facts=None):
+        """Training through the AR stack with z a constant: one forward kernel, one backward kernel."""
+        arch, (D, _, L, U), stats_graph, f32, _, _ = facts or self._facts(z, params)
+        return (arch == "AR" and getattr(self, "fused_ar_training", True) and torch.is_grad_enabled()
+                and not stats_graph and params.requires_grad and not z.requires_grad and z.dim() == 3 and f32
+                and z.size(0) == max(z.size(0), params.size(0))
+                and ops.ar_flow_supported(D, L, U) and ops.ar_flow_train_supported(z.size(0), params.size(0), D, L, U))
 
     def _ar_args(self):
         maf, bn = self.bijectors[0], self.bijectors[1]
         mean, alpha = bn._stats_for(None)  # device copies, made once per version of the statistics
         return (maf._masks_for(torch.float32), mean.detach(), alpha.detach(), self.D, self.num_layers, self.num_units)
+
+    def _flow_args(self):
+        """The arguments every coupling flow kernel shares: (2S, D) statistics and the shape."""
+        mean, alpha = self._bn_stats(_lib.require_device())
+        return (mean, alpha, self.D, self.num_stages, self.num_layers, self.num_units)
 
     def _whole_flow(self):
         """Does the fused coupling path run as ONE kernel (the only one with a fused support stage)?"""
@@ -195,7 +256,7 @@ class NormFlow(DensityEstimator):
 
     def _fused_support(self):
         """The (7, D) device constants of a ToInterval support layer that the one-kernel paths evaluate in
-        their load / store stage, or None (no support layer).  Other support layers are not fused."""
+        their load / store stage, or None (no support layer).  Other support layers are not fused: False."""
         if self._n_core == len(self.bijectors):
             return None
         sup = self.bijectors[-1]
@@ -214,35 +275,69 @@ class NormFlow(DensityEstimator):
         return torch.is_grad_enabled() and any(b.get_last_mean().requires_grad or b.get_last_alpha().requires_grad
                                                for b in self._bn_layers())
 
-    def _fused_ok(self, z, params):
+    def _fused_ok(self, z, params, facts=None):
         """One-call fused path: coupling stack, float32, no autograd, MFMA-covered shape."""
-        if self.arch_type != "coupling" or self._stats_in_graph():
-            return False
-        if z.dtype != torch.float32 or params.dtype != torch.float32:
-            return False
-        if torch.is_grad_enabled() and (z.requires_grad or params.requires_grad):
-            return False
-        # per-context weights with very few samples each (the SNPE layout, N = 1): the prepared
-        # operand images (~100 KB per context) would outweigh the samples; compose per bijector
-        if params.size(0) > 1 and z.size(1) < 32:
-            return False
-        return ops.has_fast_path(self.D, self.num_layers, self.num_units)
+        _, (D, _, L, U), _, _, _, inference = facts or self._facts(z, params)
+        return inference and ops.has_fast_path(D, L, U)
 
-    def _padded_ok(self, z, params):
+    def _padded_ok(self, z, params, facts=None):
         """One-call whole-flow kernel in its padded layouts (every 2 <= D <= 63 but 32, num_units <= 16): the
         conditions of `_fused_ok`, a 3-d z, and the fusion setting AUTO or FLOW -- FUSE_LAYER keeps the per-layer
         routes of these shapes (the wide chain, or the per-bijector composition)."""
-        if self.arch_type != "coupling" or self._stats_in_graph() or z.dim() != 3:
-            return False
-        if z.dtype != torch.float32 or params.dtype != torch.float32:
-            return False
-        if torch.is_grad_enabled() and (z.requires_grad or params.requires_grad):
-            return False
-        if params.size(0) > 1 and z.size(1) < 32:
-            return False
-        if self.fusion not in (_lib.FUSE_AUTO, _lib.FUSE_FLOW):
-            return False
-        return ops.flow_padded_supported(self.D, self.num_stages, self.num_layers, self.num_units)
+        _, shape, _, _, _, inference = facts or self._facts(z, params)
+        return (inference and z.dim() == 3 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
+                and ops.flow_padded_supported(*shape))
+
+    def _train_path(self, z, params, stats_graph=None):
+        """The fused training pair of a coupling log_prob: "reversible" (whole-flow forward, one-kernel backward from
+        z0), "layers" (one fused kernel per layer each way, for the shapes that pair does not cover) or None."""
+        if self._stats_in_graph() if stats_graph is None else stats_graph:
+            return None  # the fused training pairs treat the statistics as constants
+        shape = (z.size(0), params.size(0), z.size(1), self.D, self.num_stages, self.num_layers, self.num_units)
+        if getattr(self, "reversible_training", True) and ops.flow_train_rev_supported(*shape):
+            return "reversible"
+        if ops.flow_train_supported(*shape):
+            return "layers"
+        return None
+
+    def _route(self, op, z, params, freeze_bn=True, f32_draw=False):
+        """THE routing decision (table in the module docstring): which kernel family runs `op` ("forward", "log_prob"
+        or "inverse") on these tensors.  Pure host logic on the flow's switches and tensor metadata; nothing is
+        staged, allocated or launched.  `f32_draw`: the base draw of a "forward" is a float32 tensor, so a
+        whole-flow kernel can write log_q itself."""
+        arch, _, stats_graph, f32, _, _ = f = self._facts(z, params)
+        sup = self.bijectors[-1].name if self._n_core < len(self.bijectors) else None
+        interval = sup == "ToInterval"  # the support layer that a one-kernel family evaluates in its load / store stage
+        if arch == "affine" or (op == "inverse" and sup is not None):
+            return _BIJECTORS
+        if arch == "AR":
+            if op == "forward" and not (freeze_bn and (interval or sup is None)):
+                return _BIJECTORS
+            if self._ar_fused_ok(z, params, f):
+                return Route("ar_fused", interval, False)
+            if op == "log_prob" and self._ar_train_ok(z, params, f):
+                return Route("ar_train", interval, False)
+            return _BIJECTORS
+        # `fused` is asked through the instance: tests switch this family (never `padded`) off with an attribute of it
+        forced = vars(self).get("_fused_ok")
+        if op == "forward" and not freeze_bn:  # fresh batch statistics
+            rows, reduce = z.size(0) * z.size(1), self.batch_stats_reduce is not None
+            if ((forced(z, params) if forced else self._fused_ok(z, params, f)) and self._batch_chain_ok(z, params)
+                    and (rows > 1 or reduce)):
+                return Route("batch_chain", False, False)
+            if f32 and not reduce and self._batch_chain_ok(z, params) and rows >= 32:
+                return Route("batch_train", False, False)
+            return _BIJECTORS
+        if self._padded_ok(z, params, f):
+            return Route("padded", False, f32_draw)
+        if forced(z, params) if forced else self._fused_ok(z, params, f):
+            whole = (f32_draw or interval) and self._whole_flow()  # the only two that ask
+            return Route("fused", interval, f32_draw) if whole else _FUSED
+        if op == "log_prob" and f32 and z.dim() == 3 and z.size(0) == max(z.size(0), params.size(0)):
+            pair = self._train_path(z, params, stats_graph)
+            if pair is not None:
+                return Route("train_" + pair, False, False)
+        return _BIJECTORS
 
     # -- sampling -----------------------------------------------------------
     def __call__(self, N=100, params=None, freeze_bn=False):
@@ -276,80 +371,27 @@ class NormFlow(DensityEstimator):
         home = params.device
         dev = _lib.require_device()
         p_dev = params if params.device == dev else params.to(dev)
-        log_q = None
         if torch.is_tensor(omega) and omega.dtype == torch.float32:
+            omega64 = None
             z = omega.detach().to(dev)  # device-side draw: no float64 round trip
-            # the base density of a float32 draw can come out of the whole-flow sampling kernel itself (below);
-            # every other route evaluates it here
-            if not (freeze_bn and (self._padded_ok(z, p_dev) or (self._fused_ok(z, p_dev) and self._whole_flow()))):
-                log_q = ops.base_log_density_f64(z)
         else:
             if torch.is_tensor(omega):
                 omega64 = omega.detach().to(device=dev, dtype=torch.float64)
             else:
                 omega64 = torch.as_tensor(np.ascontiguousarray(omega), dtype=torch.float64).to(dev)
             z = omega64.float()
-            log_q = ops.base_log_density_f64(omega64)
-
-        sup = self._fused_support()
-        support_done = False
+        route = self._route("forward", z, p_dev, freeze_bn, f32_draw=omega64 is None)
+        family, omega_dev = route.family, z
+        # the base density of a float32 draw can come out of the whole-flow sampling kernels themselves
+        log_q = None if route.writes_log_q else ops.base_log_density_f64(z if omega64 is None else omega64)
+        consts = self._fused_support() if route.fuse_support else None
         # sample-sharded batch statistics (self.batch_stats_reduce): the stepwise no-autograd chain exchanges the moments
         # between its launches; every other case -- autograd, other shapes, arch_type "AR" -- runs the per-bijector
         # composition with BatchNorm layers that exchange their moments forward and their gradient sums backward
         # (ops._BnBatchShardedFn).  The one-node training chain computes local moments inside one C call: not offered.
         for b in self._bn_layers():
             b.stats_reduce = None if freeze_bn else self.batch_stats_reduce
-        if freeze_bn and self._ar_fused_ok(z, p_dev) and sup is not False:
-            z, sld = ops.ar_flow_forward_raw(z, p_dev, *self._ar_args(), interval_consts=sup)
-            log_q = log_q - sld
-            support_done = True
-        elif freeze_bn and self._padded_ok(z, p_dev):
-            # the padded whole-flow kernel (no fused support layer: it runs below as its own kernel)
-            mean, alpha = self._bn_stats(dev)
-            args = (mean, alpha, self.D, self.num_stages, self.num_layers, self.num_units)
-            if log_q is None:
-                z, sld, log_q = ops.flow_padded_forward_raw(z, p_dev, *args, want_log_q=True)
-            else:
-                z, sld = ops.flow_padded_forward_raw(z, p_dev, *args)
-                log_q = log_q - sld
-        elif freeze_bn and self._fused_ok(z, p_dev):
-            mean, alpha = self._bn_stats(dev)
-            fuse_sup = (sup is not None and sup is not False and self._whole_flow())
-            if log_q is None:  # float32 device draw on the whole-flow kernel: it writes log N(omega) - sld itself
-                omega_dev = z
-                z, sld, log_q = ops.flow_forward_raw(z, p_dev, mean, alpha, self.D, self.num_stages, self.num_layers,
-                                                     self.num_units, self.fusion,
-                                                     interval_consts=sup if fuse_sup else None, want_log_q=True)
-                if log_q is None:
-                    log_q = ops.base_log_density_f64(omega_dev) - sld
-            else:
-                z, sld = ops.flow_forward_raw(z, p_dev, mean, alpha, self.D, self.num_stages,
-                                              self.num_layers, self.num_units, self.fusion,
-                                              interval_consts=sup if fuse_sup else None)
-                log_q = log_q - sld
-            support_done = fuse_sup
-        elif (not freeze_bn and self._fused_ok(z, p_dev) and self._batch_chain_ok(z, p_dev)
-              and (z.size(0) * z.size(1) > 1 or self.batch_stats_reduce is not None)):
-            # fresh batch statistics, no autograd: one call for the whole stack; every BatchNorm layer ends up with
-            # the statistics its own forward(use_last=False) would have cached
-            bns = self._bn_layers()
-            z, sld, means, alphas = ops.flow_forward_batch_raw(z, p_dev, self.D, self.num_stages, self.num_layers,
-                                                               self.num_units, bns[0].eps,
-                                                               reduce_moments=self.batch_stats_reduce)
-            for i, b in enumerate(bns):
-                b.set_last_stats(means[i], alphas[i])
-            log_q = log_q - sld
-        elif (not freeze_bn and self.arch_type == "coupling" and z.dtype == torch.float32 and self.batch_stats_reduce is None
-              and p_dev.dtype == torch.float32 and self._batch_chain_ok(z, p_dev) and z.size(0) * z.size(1) >= 32):
-            # fresh batch statistics under autograd: one node for the whole stack (gradients through the batch
-            # moments included)
-            bns = self._bn_layers()
-            z, sld, means, alphas = ops.flow_forward_train(z, p_dev, self.D, self.num_stages, self.num_layers,
-                                                           self.num_units, bns[0].eps)
-            for i, b in enumerate(bns):
-                b.set_last_stats(means[i], alphas[i])
-            log_q = log_q - sld
-        else:
+        if family == "bijectors":
             idx = 0
             for bijector in self.bijectors[:self._n_core]:
                 if bijector.name == "BatchNorm":
@@ -359,33 +401,60 @@ class NormFlow(DensityEstimator):
                     z, log_det = bijector(z, p_dev[:, idx:idx + n])
                     idx += n
                 log_q = log_q - log_det
-        for bijector in ([] if support_done else self.bijectors[self._n_core:]):  # parameter-free support layer (:385-386)
-            z, log_det = bijector(z)
-            log_q = log_q - log_det
+        else:
+            written = None
+            if family == "ar_fused":
+                z, sld = ops.ar_flow_forward_raw(z, p_dev, *self._ar_args(), interval_consts=consts)
+            elif family == "padded":  # no fused support layer: it runs below as its own kernel
+                z, sld, *written = ops.flow_padded_forward_raw(z, p_dev, *self._flow_args(),
+                                                               want_log_q=route.writes_log_q)
+            elif family == "fused":  # `written` stays None where the selected kernel variant has no log_q output
+                z, sld, *written = ops.flow_forward_raw(z, p_dev, *self._flow_args(), self.fusion, interval_consts=consts,
+                                                        want_log_q=route.writes_log_q)
+            else:
+                # fresh batch statistics in one call for the whole stack -- "batch_chain" without autograd, "batch_train"
+                # as one node (gradients through the batch moments included); every BatchNorm layer ends up with the
+                # statistics its own forward(use_last=False) would have cached
+                bns = self._bn_layers()
+                shape = (self.D, self.num_stages, self.num_layers, self.num_units, bns[0].eps)
+                if family == "batch_chain":
+                    z, sld, means, alphas = ops.flow_forward_batch_raw(z, p_dev, *shape,
+                                                                       reduce_moments=self.batch_stats_reduce)
+                else:
+                    z, sld, means, alphas = ops.flow_forward_train(z, p_dev, *shape)
+                for i, b in enumerate(bns):
+                    b.set_last_stats(means[i], alphas[i])
+            if written and written[0] is not None:
+                log_q = written[0]
+            else:
+                log_q = (ops.base_log_density_f64(omega_dev) if log_q is None else log_q) - sld
+        if not route.fuse_support:
+            for bijector in self.bijectors[self._n_core:]:  # parameter-free support layer (:385-386)
+                z, log_det = bijector(z)
+                log_q = log_q - log_det
         if home != dev:
             z, log_q = z.to(home), log_q.to(home)
         return z, log_q
 
     # -- density ------------------------------------------------------------
+    def _fused_density(self, family, z, params, consts=None, want_lp=True, want_z0=False, want_sld=False):
+        """(log_prob | None, z0 | None, sum_log_det | None) from the one-kernel family named."""
+        if family == "ar_fused":
+            return ops.ar_flow_log_prob_raw(z, params, *self._ar_args(), want_lp=want_lp, want_z0=want_z0,
+                                            want_sld=want_sld, interval_consts=consts)
+        if family == "padded":
+            return ops.flow_padded_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
+                                                want_sld=want_sld)
+        return ops.flow_log_prob_raw(z, params, *self._flow_args(), self.fusion, want_lp=want_lp, want_z0=want_z0,
+                                     want_sld=want_sld, interval_consts=consts)
+
     def inverse_and_log_det(self, z, params):
         """Map z back to the base space, accumulating the forward log-dets
         (density_estimator.py:390-406).  Returns (z0, sum_log_det float32 (M,N))."""
-        if self._n_core == len(self.bijectors) and self._ar_fused_ok(z, params):
-            _, z0, sld = ops.ar_flow_log_prob_raw(z, params, *self._ar_args(), want_lp=False, want_z0=True, want_sld=True)
-            return z0, sld
-        if self._n_core == len(self.bijectors) and self._padded_ok(z, params):
-            mean, alpha = self._bn_stats(_lib.require_device())
-            _, z0, sld = ops.flow_padded_log_prob_raw(z, params, mean, alpha, self.D, self.num_stages, self.num_layers,
-                                                      self.num_units, want_z0=True, want_sld=True, want_lp=False)
-            return z0, sld
-        if self._n_core == len(self.bijectors) and self._fused_ok(z, params):
-            dev = _lib.require_device()
-            mean, alpha = self._bn_stats(dev)
-            _, z0, sld = ops.flow_log_prob_raw(z, params, mean, alpha, self.D, self.num_stages,
-                                               self.num_layers, self.num_units, self.fusion,
-                                               want_z0=True, want_sld=True, want_lp=False)
-            return z0, sld
-        return self._core_inverse(z, params, self.bijectors)
+        family = self._route("inverse", z, params).family
+        if family == "bijectors":
+            return self._core_inverse(z, params, self.bijectors)
+        return self._fused_density(family, z, params, want_z0=True, want_sld=True, want_lp=False)[1:]
 
     def _core_inverse(self, z, params, bijectors=None):
         """The reference's loop, one HIP kernel per bijector (the whole stack, or only its
@@ -418,68 +487,22 @@ class NormFlow(DensityEstimator):
         """log q(z) (density_estimator.py:408-416)."""
         if not self.conditioner:
             params = self.params
-        if self._n_core < len(self.bijectors):
-            sup = self._fused_support()
-            if sup is not False and self._ar_fused_ok(z, params):
-                # ToInterval^-1 in the load stage of the one-kernel AR path
-                return ops.ar_flow_log_prob_raw(z, params, *self._ar_args(), interval_consts=sup)[0]
-            if sup is not False and self._ar_train_ok(z, params):
-                masks, mean, alpha, D, L, U = self._ar_args()
-                return ops.ar_flow_log_prob_train(z, params, masks, mean, alpha, sup, D, L, U)
-            if sup is not False and not self._padded_ok(z, params) and self._fused_ok(z, params) and self._whole_flow():
-                mean, alpha = self._bn_stats(_lib.require_device())  # ... or of the whole-flow coupling kernel
-                return ops.flow_log_prob_raw(z, params, mean, alpha, self.D, self.num_stages, self.num_layers,
-                                             self.num_units, self.fusion, interval_consts=sup)[0]
+        family, fuse_support, _ = self._route("log_prob", z, params)
+        consts = self._fused_support() if fuse_support else None  # ToInterval^-1 in the kernel's load stage
+        ld_support = None
+        if self._n_core < len(self.bijectors) and not fuse_support:
             # support layer first (it is the last bijector of the stack), then the core's density:
             # log q(z) = log q_core(s^-1(z)) - log|det ds| -- same sum as density_estimator.py:395-416
-            zc, ld_support = self.bijectors[-1].inverse_and_log_det(z)
-            return self._core_log_prob(zc, params) - ld_support
-        return self._core_log_prob(z, params)
-
-    def _train_path(self, z, params):
-        if self._stats_in_graph():
-            return None  # the fused training pairs treat the statistics as constants
-        shape = (z.size(0), params.size(0), z.size(1), self.D, self.num_stages, self.num_layers, self.num_units)
-        if getattr(self, "reversible_training", True) and ops.flow_train_rev_supported(*shape):
-            return "reversible"
-        if ops.flow_train_supported(*shape):
-            return "layers"
-        return None
-
-    def _ar_train_ok(self, z, params):
-        """Training through the AR stack with z a constant: one forward kernel, one backward kernel."""
-        return (self.arch_type == "AR" and getattr(self, "fused_ar_training", True) and torch.is_grad_enabled()
-                and not self._stats_in_graph()
-                and params.requires_grad and not z.requires_grad and z.dim() == 3
-                and z.dtype == torch.float32 and params.dtype == torch.float32
-                and z.size(0) == max(z.size(0), params.size(0))
-                and ops.ar_flow_supported(self.D, self.num_layers, self.num_units)
-                and ops.ar_flow_train_supported(z.size(0), params.size(0), self.D, self.num_layers, self.num_units))
-
-    def _core_log_prob(self, z, params):
-        if self._ar_fused_ok(z, params):
-            return ops.ar_flow_log_prob_raw(z, params, *self._ar_args())[0]
-        if self._ar_train_ok(z, params):
+            z, ld_support = self.bijectors[-1].inverse_and_log_det(z)
+        if family in ("ar_fused", "padded", "fused"):
+            log_q = self._fused_density(family, z, params, consts)[0]
+        elif family == "ar_train":
             masks, mean, alpha, D, L, U = self._ar_args()
-            return ops.ar_flow_log_prob_train(z, params, masks, mean, alpha, None, D, L, U)
-        if self._padded_ok(z, params):
-            mean, alpha = self._bn_stats(_lib.require_device())
-            return ops.flow_padded_log_prob_raw(z, params, mean, alpha, self.D, self.num_stages, self.num_layers,
-                                                self.num_units)[0]
-        if self._fused_ok(z, params):
-            dev = _lib.require_device()
-            mean, alpha = self._bn_stats(dev)
-            lp, _, _ = ops.flow_log_prob_raw(z, params, mean, alpha, self.D, self.num_stages,
-                                             self.num_layers, self.num_units, self.fusion)
-            return lp
-        if (self.arch_type == "coupling" and z.dtype == torch.float32 and params.dtype == torch.float32
-                and z.dim() == 3 and z.size(0) == max(z.size(0), params.size(0))
-                and self._train_path(z, params) is not None):
-            # training (BatchNorm stats constant): the reversible pair -- whole-flow forward, one-kernel
-            # backward from z0 -- or, for the shapes it does not cover, one fused kernel per layer each way
-            mean, alpha = self._bn_stats(_lib.require_device())
-            return ops.flow_log_prob_train(z, params, mean, alpha, self.D, self.num_stages, self.num_layers,
-                                           self.num_units, reversible=self._train_path(z, params) == "reversible")
-        z0, sum_log_det = self._core_inverse(z, params)
-        log_q = torch.sum(-(z0 ** 2), axis=2) / 2.0 - self.D * np.log(np.sqrt(2.0 * np.pi))
-        return log_q - sum_log_det
+            log_q = ops.ar_flow_log_prob_train(z, params, masks, mean, alpha, consts, D, L, U)
+        elif family != "bijectors":  # training with the BatchNorm statistics constant, one of the two fused pairs
+            log_q = ops.flow_log_prob_train(z, params, *self._flow_args(), reversible=family == "train_reversible")
+        else:
+            z0, sum_log_det = self._core_inverse(z, params)
+            log_q = torch.sum(-(z0 ** 2), axis=2) / 2.0 - self.D * np.log(np.sqrt(2.0 * np.pi))
+            log_q = log_q - sum_log_det
+        return log_q if ld_support is None else log_q - ld_support
