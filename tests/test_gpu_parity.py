@@ -434,6 +434,129 @@ def test_host_tensors_are_staged(tnf, oracle):
     torch.testing.assert_close(ld, ld_want, rtol=1e-12, atol=1e-12)
 
 
+def _host_cases(tnf):
+    """name -> (call, differentiable inputs): every `*_raw` entry and every differentiable entry of ops.py on CPU inputs."""
+    ops, L_ = tnf.ops, tnf._lib
+    D, S, L, U, M, N, H = 8, 2, 2, 15, 2, 40, 50
+    g = torch.Generator().manual_seed(0)
+
+    def rnd(*shape, grad=False, scale=0.1):
+        return (torch.randn(*shape, generator=g) * scale).requires_grad_(grad)
+
+    nvp, aff, maf = tnf.RealNVP(D, L, U), tnf.Affine(D), tnf.MAF(D, L, U)
+    nf = tnf.NormFlow(D, True, "coupling", S, L, U)
+    nf64 = tnf.NormFlow(64, True, "coupling", S, L, U)
+    ar = tnf.NormFlow(D, True, "AR", 1, L, U)
+    masks, ar_masks = maf._masks_flat, ar.bijectors[0]._masks_flat
+    consts = tnf.ToInterval(D, [-1.0] * D, [2.0] * D)._consts
+    mean, alpha = rnd(2 * S, D), 1 + rnd(2 * S, D).abs()
+    ident = lambda t: t  # noqa: E731
+    z, zg, z1, zp = rnd(M, N, D, scale=1), rnd(M, N, D, grad=True, scale=1), rnd(1, N, D, scale=1), rnd(M, N, D, scale=1).abs()
+    z64, z64g = rnd(1, N, 64, scale=1), rnd(1, N, 64, grad=True, scale=1)
+    p_nvp, p_aff, p_maf = (rnd(M, b.count_num_params(), grad=True) for b in (nvp, aff, maf))
+    p_nf, p_nf64, p_ar = rnd(1, nf.D_params, grad=True), rnd(1, nf64.D_params, grad=True), rnd(1, ar.D_params, grad=True)
+    mean64, alpha64 = rnd(2 * S, 64), 1 + rnd(2 * S, 64).abs()
+    h, w, b = rnd(M, H, grad=True), rnd(nf64.D_params, H, grad=True), rnd(nf64.D_params, grad=True)
+    eta = rnd(M, ops.ef_num_eta(L_.EF_MVN, D), grad=True)
+    return {
+        "coupling_raw": (lambda: ops.coupling_raw(z, p_nvp.detach(), D, L, U, True, False), ()),
+        "coupling": (lambda: ops.coupling(zg, p_nvp, D, L, U, True, False), (zg, p_nvp)),
+        "affine_raw": (lambda: ops.affine_raw(z, p_aff.detach(), D, False), ()),
+        "affine": (lambda: ops.affine(zg, p_aff, D, True), (zg, p_aff)),
+        "bn_apply_raw": (lambda: ops.bn_apply_raw(z, mean[0], alpha[0], False), ()),
+        "bn_apply": (lambda: ops.bn_apply(zg, mean[0], alpha[0], True), (zg,)),
+        "bn_batch_forward": (lambda: ops.bn_batch_forward(zg, 1e-5), (zg,)),
+        "bn_batch_forward_no_grad": (lambda: ops.bn_batch_forward(z, 1e-5), ()),
+        "bn_batch_forward_sharded": (lambda: ops.bn_batch_forward(zg, 1e-5, ident), (zg,)),
+        "base_log_density_f64": (lambda: ops.base_log_density_f64(z), ()),
+        "flow_log_prob_raw": (lambda: ops.flow_log_prob_raw(z64, p_nf64.detach(), mean64, alpha64, 64, S, L, U, want_z0=True,
+                                                            want_sld=True, count_reruns=True), ()),
+        "flow_forward_raw": (lambda: ops.flow_forward_raw(z64, p_nf64.detach(), mean64, alpha64, 64, S, L, U,
+                                                          want_log_q=True), ()),
+        "flow_padded_log_prob_raw": (lambda: ops.flow_padded_log_prob_raw(z1, p_nf.detach(), mean, alpha, D, S, L, U,
+                                                                          want_z0=True, want_sld=True, count_reruns=True), ()),
+        "flow_padded_forward_raw": (lambda: ops.flow_padded_forward_raw(z1, p_nf.detach(), mean, alpha, D, S, L, U,
+                                                                        want_log_q=True), ()),
+        "flow_forward_batch_raw": (lambda: ops.flow_forward_batch_raw(z64, p_nf64, 64, S, L, U, 1e-5), ()),
+        "flow_forward_batch_raw_reduce": (lambda: ops.flow_forward_batch_raw(z64, p_nf64, 64, S, L, U, 1e-5, ident), ()),
+        "flow_forward_train": (lambda: ops.flow_forward_train(z64g, p_nf64, 64, S, L, U, 1e-5)[:2], (z64g, p_nf64)),
+        "flow_forward_train_stats": (lambda: ops.flow_forward_train(z64, p_nf64, 64, S, L, U, 1e-5)[2:], ()),
+        "flow_log_prob_train_rev": (lambda: ops.flow_log_prob_train(z64g, p_nf64, mean64, alpha64, 64, S, L, U),
+                                    (z64g, p_nf64)),
+        "flow_log_prob_train_layers": (lambda: ops.flow_log_prob_train(z64g, p_nf64, mean64, alpha64, 64, S, L, U,
+                                                                       reversible=False), (z64g, p_nf64)),
+        "maf_raw": (lambda: ops.maf_raw(z, p_maf.detach(), masks, D, L, U, True), ()),
+        "maf_inverse_alpha_raw": (lambda: ops.maf_inverse_alpha_raw(z, p_maf.detach(), masks, D, L, U), ()),
+        "maf_inverse": (lambda: ops.maf(zg, p_maf, masks, D, L, U, True), (zg, p_maf)),
+        "maf_forward": (lambda: ops.maf(zg, p_maf, masks, D, L, U, False), (zg, p_maf)),
+        "to_interval_raw": (lambda: ops.to_interval_raw(z, consts, False), ()),
+        "to_interval": (lambda: ops.to_interval(zg, consts, False), (zg,)),
+        "to_simplex_raw": (lambda: ops.to_simplex_raw(z, D + 1), ()),
+        "to_simplex": (lambda: ops.to_simplex(zg, D + 1), (zg,)),
+        "ef_suffstats_raw": (lambda: ops.ef_suffstats_raw(z, L_.EF_MVN), ()),
+        "ef_suffstats": (lambda: ops.ef_suffstats(zg, L_.EF_MVN), (zg,)),
+        "ef_dot_raw": (lambda: ops.ef_dot_raw(zp, eta.detach(), L_.EF_MVN), ()),
+        "ef_dot": (lambda: ops.ef_dot(zg, eta, L_.EF_MVN), (zg, eta)),
+        "cond_flow_log_prob_raw": (lambda: ops.cond_flow_log_prob_raw(z64[0, :M], h.detach(), w.detach(), b.detach(), mean64,
+                                                                      alpha64, 64, S, L, U, want_z0=True, want_sld=True), ()),
+        "cond_flow_forward_raw": (lambda: ops.cond_flow_forward_raw(z64[0, :M], h.detach(), w.detach(), b.detach(), mean64,
+                                                                    alpha64, 64, S, L, U), ()),
+        "cond_flow_log_prob_train": (lambda: ops.cond_flow_log_prob_train(z64g[0, :M], h, w, b, mean64, alpha64, 64, S, L, U),
+                                     (z64g, h, w, b)),
+        "ar_flow_log_prob_raw": (lambda: ops.ar_flow_log_prob_raw(z1, p_ar.detach(), ar_masks, mean[0], alpha[0], D, L, U,
+                                                                  want_z0=True, want_sld=True), ()),
+        "ar_flow_forward_raw": (lambda: ops.ar_flow_forward_raw(z1, p_ar.detach(), ar_masks, mean[0], alpha[0], D, L, U), ()),
+        "ar_flow_log_prob_train": (lambda: ops.ar_flow_log_prob_train(z1, p_ar, ar_masks, mean[0], alpha[0], None, D, L, U),
+                                   (p_ar,)),
+    }
+
+
+# What comes back for CPU inputs, recorded once from the code this table was written against: the device type of every
+# returned tensor and of every gradient.  "cuda" = handed out on the compute device on purpose (the caller keeps working
+# there): the batch-statistics chains, the fused conditional flow, the AR sampler, f_alpha, the rerun counters.
+HOST_DEVICES = {
+    "coupling_raw": ("cpu cpu", ""), "coupling": ("cpu cpu", "cpu cpu"),
+    "affine_raw": ("cpu cpu", ""), "affine": ("cpu cpu", "cpu cpu"),
+    "bn_apply_raw": ("cpu cpu", ""), "bn_apply": ("cpu cpu", "cpu"),
+    "bn_batch_forward": ("cpu cpu cpu cpu", "cpu"), "bn_batch_forward_no_grad": ("cpu cpu cpu cpu", ""),
+    "bn_batch_forward_sharded": ("cpu cpu cpu cpu", "cpu"),
+    "base_log_density_f64": ("cpu", ""),
+    "flow_log_prob_raw": ("cpu cpu cpu cuda", ""), "flow_forward_raw": ("cpu cpu cpu", ""),
+    "flow_padded_log_prob_raw": ("cpu cpu cpu cuda", ""), "flow_padded_forward_raw": ("cpu cpu cpu", ""),
+    "flow_forward_batch_raw": ("cuda cuda cuda cuda", ""), "flow_forward_batch_raw_reduce": ("cuda cuda cuda cuda", ""),
+    "flow_forward_train": ("cuda cuda", "cpu cpu"), "flow_forward_train_stats": ("cuda cuda", ""),
+    "flow_log_prob_train_rev": ("cpu", "cpu cpu"), "flow_log_prob_train_layers": ("cpu", "cpu cpu"),
+    "maf_raw": ("cpu cpu", ""), "maf_inverse_alpha_raw": ("cuda", ""),
+    "maf_inverse": ("cpu cpu", "cpu cpu"), "maf_forward": ("cpu cpu", "cpu cpu"),
+    "to_interval_raw": ("cpu cpu", ""), "to_interval": ("cpu cpu", "cpu"),
+    "to_simplex_raw": ("cpu cpu", ""), "to_simplex": ("cpu cpu", "cpu"),
+    "ef_suffstats_raw": ("cpu", ""), "ef_suffstats": ("cpu", "cpu"),
+    "ef_dot_raw": ("cpu", ""), "ef_dot": ("cpu", "cpu cpu"),
+    "cond_flow_log_prob_raw": ("cuda cuda cuda", ""), "cond_flow_forward_raw": ("cuda cuda", ""),
+    "cond_flow_log_prob_train": ("cuda", "cpu cpu cpu cpu"),
+    "ar_flow_log_prob_raw": ("cpu cpu cpu", ""), "ar_flow_forward_raw": ("cuda cuda", ""),
+    "ar_flow_log_prob_train": ("cpu", "cpu"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(HOST_DEVICES))
+def test_host_inputs_come_back_where_recorded(tnf, name):
+    """CPU tensors in: which device every result and every gradient of every ops entry lives on (HOST_DEVICES)."""
+    call, wrt = _host_cases(tnf)[name]
+    out = call()
+    outs = out if isinstance(out, (tuple, list)) else (out,)
+    got = " ".join(t.device.type for t in outs)
+    grads = ""
+    if wrt:
+        diff = [t for t in outs if t.requires_grad]
+        gs = torch.autograd.grad(diff, wrt, [torch.ones_like(t) for t in diff])
+        grads = " ".join(t.device.type for t in gs)
+    torch.cuda.synchronize()
+    print("host devices %s: outputs [%s] gradients [%s]" % (name, got, grads))
+    assert (got, grads) == HOST_DEVICES[name]
+    assert all(torch.isfinite(t.float()).all() for t in outs if t.dtype.is_floating_point)
+
+
 # --------------------------------------------------------------------------
 # 3. properties at the benchmark size
 # --------------------------------------------------------------------------

@@ -5,6 +5,7 @@ in-tree by `__graft_entry__.build()` / `make -C torch_nf_amd/csrc`; if it is
 missing the import fails loudly -- there is no CPU or PyTorch fallback for the
 flow arithmetic anywhere in this package.
 """
+import contextlib
 import ctypes
 import os
 
@@ -196,6 +197,21 @@ def options_snapshot():
         check(lib.tnf_get_option(key, ctypes.addressof(val)))
         out.append(val.value)
     return tuple(out)
+
+
+@contextlib.contextmanager
+def option_set(key, value, restore=None):
+    """`with option_set(key, value)`: one thread-local option set for a block, its previous value back afterwards
+    (`restore`: that value, from a caller that keeps track of it itself)."""
+    if restore is None:
+        before = ctypes.c_int32(0)
+        check(lib.tnf_get_option(key, ctypes.addressof(before)))
+        restore = before.value
+    check(lib.tnf_set_option(key, value))
+    try:
+        yield
+    finally:
+        check(lib.tnf_set_option(key, restore))
 
 
 class options_reentered(object):

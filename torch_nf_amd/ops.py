@@ -5,6 +5,9 @@ the current stream, and autograd bookkeeping.  Inputs that live on the host are
 staged to the HIP device and results are handed back on the input's device, so
 code written against the reference (which is CPU-only) keeps working -- but the
 arithmetic always runs on the GPU; there is no CPU implementation here.
+
+Every entry is the same four steps in the vocabulary of _staging.py: stage the inputs, allocate the outputs, one
+`lib.tnf_*` call, `_home` the results.  An entry that returns on the compute device says so and does not call `_home`.
 """
 import contextlib
 import functools
@@ -14,8 +17,8 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-
-_DTYPES = {torch.float32: _lib.F32, torch.float64: _lib.F64}
+from ._staging import (_check3, _dtype_code, _grad_or_zeros, _home, _masks, _pair, _ptr, _rows, _stage, _stats, _workspace,
+                       _ws, _ws_cache)  # noqa: F401 -- _workspace, _ws_cache: looked up here by tools and tests
 
 
 def _records_options(fn):
@@ -38,50 +41,6 @@ def _reenters_options(fn):
     return staticmethod(backward)
 
 
-def _dtype_code(t):
-    try:
-        return _DTYPES[t.dtype]
-    except KeyError:
-        raise TypeError("torch_nf_amd kernels take float32 or float64 tensors, not %s" % t.dtype)
-
-
-def _stage(t, dev):
-    """Contiguous copy/view of `t` on the compute device."""
-    if t.device != dev:
-        t = t.to(dev)
-    return t.contiguous()
-
-
-def _stats(t, dev):
-    """BatchNorm statistics as contiguous float32 on the device (no-op when they already are)."""
-    if t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and not t.requires_grad:
-        return t
-    return _stage(t.detach().float(), dev)
-
-
-def _rows(params, dev):
-    """(M_p, P) parameter rows with unit inner stride -> (tensor, row_stride)."""
-    if params.dim() != 2:
-        raise ValueError("params must be (M, D_params), got shape %s" % (tuple(params.shape),))
-    if params.device != dev:
-        params = params.to(dev)
-    if params.stride(1) != 1 or (params.shape[0] > 1 and params.stride(0) < params.shape[1]):
-        params = params.contiguous()
-    stride = params.stride(0) if params.shape[0] > 1 else max(params.stride(0), params.shape[1])
-    return params, stride
-
-
-def _bcast_M(Mz, Mp):
-    if Mz != Mp and Mz != 1 and Mp != 1:
-        raise RuntimeError("batch dimensions of z (%d) and params (%d) do not broadcast" % (Mz, Mp))
-    return max(Mz, Mp)
-
-
-def _check3(z):
-    if z.dim() != 3:
-        raise ValueError("z must be (M, N, D), got shape %s" % (tuple(z.shape),))
-
-
 # ---------------------------------------------------------------------------
 # RealNVP coupling layer
 # ---------------------------------------------------------------------------
@@ -89,27 +48,15 @@ def coupling_raw(z, params, D, L, U, upper, inverse):
     """No-autograd call of tnf_coupling.  Returns (z_out (M,N,D), log_det (M,N))."""
     _check3(z)
     dev = _lib.require_device()
-    home = z.device
     code = _dtype_code(z)
-    if params.dtype != z.dtype:
-        raise TypeError("z (%s) and params (%s) must have the same dtype" % (z.dtype, params.dtype))
-    zc = _stage(z, dev)
-    pc, pstride = _rows(params, dev)
-    Mz, N = zc.shape[0], zc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
-    if zc.shape[2] != D:
-        raise ValueError("last dimension of z (%d) must equal D (%d)" % (zc.shape[2], D))
+    zc, pc, pstride, Mz, Mp, M, N = _pair(z, params, dev, D, same_dtype=True)
     z_out = torch.empty((M, N, D), dtype=z.dtype, device=dev)
     log_det = torch.empty((M, N), dtype=z.dtype, device=dev)
-    if N == 0:
-        return z_out.to(home), log_det.to(home)
-    check(lib.tnf_coupling(code, zc.data_ptr(), pc.data_ptr(), z_out.data_ptr(), log_det.data_ptr(),
-                           Mz, Mp, N, D, L, U, int(upper), int(inverse), pstride, _lib.LD_STORE,
-                           _lib.stream_ptr()))
-    if home != dev:
-        z_out, log_det = z_out.to(home), log_det.to(home)
-    return z_out, log_det
+    if N > 0:
+        check(lib.tnf_coupling(code, zc.data_ptr(), pc.data_ptr(), z_out.data_ptr(), log_det.data_ptr(),
+                               Mz, Mp, N, D, L, U, int(upper), int(inverse), pstride, _lib.LD_STORE,
+                               _lib.stream_ptr()))
+    return _home((z_out, log_det), z.device, dev)
 
 
 class _CouplingFn(torch.autograd.Function):
@@ -141,24 +88,13 @@ def coupling(z, params, D, L, U, upper, inverse):
 def affine_raw(z, params, D, inverse):
     _check3(z)
     dev = _lib.require_device()
-    home = z.device
     code = _dtype_code(z)
-    if params.dtype != z.dtype:
-        raise TypeError("z (%s) and params (%s) must have the same dtype" % (z.dtype, params.dtype))
-    zc = _stage(z, dev)
-    pc, pstride = _rows(params, dev)
-    Mz, N = zc.shape[0], zc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
-    if zc.shape[2] != D:
-        raise ValueError("last dimension of z (%d) must equal D (%d)" % (zc.shape[2], D))
+    zc, pc, pstride, Mz, Mp, M, N = _pair(z, params, dev, D, same_dtype=True)
     z_out = torch.empty((M, N, D), dtype=z.dtype, device=dev)
     log_det = torch.empty((Mp, 1), dtype=z.dtype, device=dev)
     check(lib.tnf_affine(code, zc.data_ptr(), pc.data_ptr(), z_out.data_ptr(), log_det.data_ptr(),
                          Mz, Mp, N, D, int(inverse), pstride, _lib.stream_ptr()))
-    if home != dev:
-        z_out, log_det = z_out.to(home), log_det.to(home)
-    return z_out, log_det
+    return _home((z_out, log_det), z.device, dev)
 
 
 class _AffineFn(torch.autograd.Function):
@@ -190,20 +126,16 @@ def affine(z, params, D, inverse):
 def bn_apply_raw(z, mean, alpha, inverse):
     _check3(z)
     dev = _lib.require_device()
-    home = z.device
     code = _dtype_code(z)
     zc = _stage(z, dev)
     D = zc.shape[2]
-    mean_c = _stage(mean.detach().float(), dev)
-    alpha_c = _stage(alpha.detach().float(), dev)
+    mean_c, alpha_c = _stats(mean, dev), _stats(alpha, dev)
     z_out = torch.empty_like(zc)
     log_det = torch.empty((), dtype=torch.float32, device=dev)
     check(lib.tnf_bn_apply(code, zc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(), z_out.data_ptr(),
                            log_det.data_ptr(), zc.shape[0] * zc.shape[1], D, int(inverse),
                            _lib.stream_ptr()))
-    if home != dev:
-        z_out, log_det = z_out.to(home), log_det.to(home)
-    return z_out, log_det
+    return _home((z_out, log_det), z.device, dev)
 
 
 class _BnApplyFn(torch.autograd.Function):
@@ -335,8 +267,8 @@ class HipBnShardKernels(object):
     def backward_apply(z_norm, g, g_ld, alpha, sums, count):
         D = z_norm.shape[-1]
         out = torch.empty_like(z_norm)
-        check(lib.tnf_bn_batch_backward_apply_f32(z_norm.data_ptr(), g.data_ptr(), None if g_ld is None else g_ld.data_ptr(),
-                                                  alpha.data_ptr(), sums.data_ptr(), count.data_ptr(), out.data_ptr(),
+        check(lib.tnf_bn_batch_backward_apply_f32(z_norm.data_ptr(), g.data_ptr(), _ptr(g_ld), alpha.data_ptr(),
+                                                  sums.data_ptr(), count.data_ptr(), out.data_ptr(),
                                                   z_norm.numel() // D, D, _lib.stream_ptr()))
         return out
 
@@ -389,20 +321,16 @@ def bn_batch_forward_sharded(z, eps, reduce, kernels=None):
     _check3(z)
     if z.dtype != torch.float32:
         raise TypeError("BatchNorm batch statistics are implemented for float32 (got %s)" % z.dtype)
-    home = z.device
     if kernels is None:
         kernels = HipBnShardKernels
-        dev = _lib.require_device()
-        zc = z if z.device == dev and z.is_contiguous() else z.to(dev).contiguous()
+        zc = _stage(z, _lib.require_device())
     else:
         zc = z.contiguous()
     if torch.is_grad_enabled() and zc.requires_grad:
         out = _BnBatchShardedFn.apply(zc, eps, reduce, kernels)
     else:
         out = kernels.normalize(zc, reduce(kernels.moments(zc)), eps)
-    if home != zc.device:
-        out = tuple(t.to(home) for t in out)
-    return out
+    return _home(tuple(out), z.device, zc.device)
 
 
 def _bn_batch_forward_raw(z, eps):
@@ -410,7 +338,6 @@ def _bn_batch_forward_raw(z, eps):
     if z.dtype != torch.float32:
         raise TypeError("BatchNorm batch statistics are implemented for float32 (got %s)" % z.dtype)
     dev = _lib.require_device()
-    home = z.device
     zc = _stage(z.detach(), dev)
     D = zc.shape[2]
     rows = zc.shape[0] * zc.shape[1]
@@ -422,13 +349,11 @@ def _bn_batch_forward_raw(z, eps):
     alpha = torch.empty(D, dtype=torch.float32, device=dev)
     log_det = torch.empty((), dtype=torch.float32, device=dev)
     ws_bytes = lib.tnf_bn_batch_workspace_bytes(D)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)  # a few bytes per feature: not worth the shared buffer
     check(lib.tnf_bn_batch_forward_f32(zc.data_ptr(), z_out.data_ptr(), mean.data_ptr(), alpha.data_ptr(),
                                        log_det.data_ptr(), rows, D, float(eps), ws.data_ptr(), ws_bytes,
                                        _lib.stream_ptr()))
-    if home != dev:
-        z_out, log_det, mean, alpha = z_out.to(home), log_det.to(home), mean.to(home), alpha.to(home)
-    return z_out, log_det, mean, alpha
+    return _home((z_out, log_det, mean, alpha), z.device, dev)
 
 
 # ---------------------------------------------------------------------------
@@ -437,13 +362,12 @@ def _bn_batch_forward_raw(z, eps):
 def base_log_density_f64(omega):
     """omega (M,N,D) float64 or float32 tensor -> (M,N) float64 log N(omega; 0, I)."""
     dev = _lib.require_device()
-    home = omega.device
     oc = _stage(omega, dev)
     code = _dtype_code(oc)
     M, N, D = oc.shape
     out = torch.empty((M, N), dtype=torch.float64, device=dev)
     check(lib.tnf_base_log_density_f64(code, oc.data_ptr(), out.data_ptr(), M * N, D, _lib.stream_ptr()))
-    return out if home == dev else out.to(home)
+    return _home(out, omega.device, dev)
 
 
 # ---------------------------------------------------------------------------
@@ -464,15 +388,13 @@ def operand_precision(prec):
     inverse and backward) round every conditioner operand to bf16.  Per thread, like every tnf_set_option key; autograd
     runs backward on its own thread, so the Functions below record the precision their forward ran in and re-enter it.
     Not a parity path: tools/bf16_sweep.py reports its error and its speed."""
-    code = _PREC_CODES[prec]
-    before = current_operand_precision()
-    check(lib.tnf_set_option(_lib.OPT_OPERAND_PREC, code))
-    _prec_state.prec = prec
-    try:
-        yield
-    finally:
-        check(lib.tnf_set_option(_lib.OPT_OPERAND_PREC, _PREC_CODES[before]))
-        _prec_state.prec = before
+    before = current_operand_precision()  # this thread's name for it, which is what comes back afterwards
+    with _lib.option_set(_lib.OPT_OPERAND_PREC, _PREC_CODES[prec], restore=_PREC_CODES[before]):
+        _prec_state.prec = prec
+        try:
+            yield
+        finally:
+            _prec_state.prec = before
 
 
 def has_fast_path(D, L, U):
@@ -486,18 +408,19 @@ def resolve_fusion(D, S, L, U, fusion):
     return fusion
 
 
-_ws_cache = {}
+def _flow_prep(z, params, bn_mean, bn_alpha):
+    """What the float32 whole-stack RealNVP entries stage -> (dev, zc, pc, pstride, mean_c, alpha_c, Mz, Mp, M, N).
+    (z: rows of D floats; the kernels need 4-byte alignment only, so a contiguous view is not copied.)"""
+    _check3(z)
+    dev = _lib.require_device()
+    if z.dtype != torch.float32 or params.dtype != torch.float32:
+        raise TypeError("the fused flow kernels are float32")
+    zc, pc, pstride, Mz, Mp, M, N = _pair(z, params, dev)
+    return dev, zc, pc, pstride, _stats(bn_mean, dev), _stats(bn_alpha, dev), Mz, Mp, M, N
 
 
-def _workspace(nbytes, dev):
-    """Grow-only scratch buffer per (device, stream); the kernels of one call are
-    stream-ordered, so reuse on the same stream is safe."""
-    key = (dev.index, _lib.stream_ptr())
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _ws_cache[key] = buf
-    return buf
+def _empty_f32(want, shape, dev):
+    return torch.empty(shape, dtype=torch.float32, device=dev) if want else None
 
 
 def flow_log_prob_raw(z, params, bn_mean, bn_alpha, D, S, L, U, fusion=_lib.FUSE_AUTO,
@@ -506,42 +429,20 @@ def flow_log_prob_raw(z, params, bn_mean, bn_alpha, D, S, L, U, fusion=_lib.FUSE
     interval_consts: (7, D) device constants of a ToInterval support layer fused into the whole-flow kernel.
     count_reruns: also return a one-element int32 device tensor = the number of 32-sample groups the whole-flow kernel
     re-ran with exact fp32 first-layer contractions (inputs outside the split-f16 operand range; tnf_flow_log_prob_diag_f32)."""
-    _check3(z)
-    dev = _lib.require_device()
-    home = z.device
-    if z.dtype != torch.float32 or params.dtype != torch.float32:
-        raise TypeError("the fused flow kernels are float32")
-    zc = _stage(z, dev)
-    pc, pstride = _rows(params, dev)
-    mean_c = _stats(bn_mean, dev)
-    alpha_c = _stats(bn_alpha, dev)
-    Mz, N = zc.shape[0], zc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
+    dev, zc, pc, pstride, mean_c, alpha_c, Mz, Mp, M, N = _flow_prep(z, params, bn_mean, bn_alpha)
     fusion = resolve_fusion(D, S, L, U, fusion)
-    lp = torch.empty((M, N), dtype=torch.float32, device=dev) if want_lp else None
-    z0 = torch.empty((M, N, D), dtype=torch.float32, device=dev) if want_z0 else None
-    sld = torch.empty((M, N), dtype=torch.float32, device=dev) if want_sld else None
+    lp, z0, sld = _empty_f32(want_lp, (M, N), dev), _empty_f32(want_z0, (M, N, D), dev), _empty_f32(want_sld, (M, N), dev)
     if N == 0:
-        return tuple(t.to(home) if t is not None else None for t in (lp, z0, sld))
-    ws_bytes = check(lib.tnf_flow_workspace_bytes(M, N, D, S, L, U, fusion))
-    ws = _workspace(ws_bytes, dev)
-    args = (zc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
-            None if interval_consts is None else interval_consts.data_ptr(),
-            lp.data_ptr() if want_lp else None, z0.data_ptr() if want_z0 else None,
-            sld.data_ptr() if want_sld else None, Mz, Mp, N, D, S, L, U, pstride, fusion, ws.data_ptr(),
-            ws.numel(), _lib.stream_ptr())
-    reruns = None
-    if count_reruns:
-        reruns = torch.zeros(1, dtype=torch.int32, device=dev)
-        check(lib.tnf_flow_log_prob_diag_f32(*args, reruns.data_ptr()))
-    else:
+        return _home((lp, z0, sld), z.device, dev)
+    ws, ws_bytes = _ws(check(lib.tnf_flow_workspace_bytes(M, N, D, S, L, U, fusion)), dev)
+    args = (zc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(), _ptr(interval_consts), _ptr(lp), _ptr(z0),
+            _ptr(sld), Mz, Mp, N, D, S, L, U, pstride, fusion, ws, ws_bytes, _lib.stream_ptr())
+    if not count_reruns:
         check(lib.tnf_flow_log_prob_f32(*args))
-    if home != dev:
-        lp = lp.to(home) if want_lp else None
-        z0 = z0.to(home) if want_z0 else None
-        sld = sld.to(home) if want_sld else None
-    return (lp, z0, sld, reruns) if count_reruns else (lp, z0, sld)
+        return _home((lp, z0, sld), z.device, dev)
+    reruns = torch.zeros(1, dtype=torch.int32, device=dev)  # stays on the compute device
+    check(lib.tnf_flow_log_prob_diag_f32(*args, reruns.data_ptr()))
+    return _home((lp, z0, sld), z.device, dev) + (reruns,)
 
 
 def flow_forward_raw(omega, params, bn_mean, bn_alpha, D, S, L, U, fusion=_lib.FUSE_AUTO, interval_consts=None,
@@ -549,46 +450,31 @@ def flow_forward_raw(omega, params, bn_mean, bn_alpha, D, S, L, U, fusion=_lib.F
     """tnf_flow_forward_f32 (frozen BatchNorm).  Returns (z (M,N,D), sum_log_det (M,N)).
     want_log_q: a third value, log_q (M,N) float64 = log N(omega; 0, I) - sum_log_det written by the whole-flow kernel
     itself (tnf_flow_forward_logq_f32), or None when the call does not run on that kernel."""
-    _check3(omega)
-    dev = _lib.require_device()
+    dev, oc, pc, pstride, mean_c, alpha_c, Mz, Mp, M, N = _flow_prep(omega, params, bn_mean, bn_alpha)
     home = omega.device
-    if omega.dtype != torch.float32 or params.dtype != torch.float32:
-        raise TypeError("the fused flow kernels are float32")
-    oc = _stage(omega, dev)
-    pc, pstride = _rows(params, dev)
-    mean_c = _stats(bn_mean, dev)
-    alpha_c = _stats(bn_alpha, dev)
-    Mz, N = oc.shape[0], oc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
     fusion = resolve_fusion(D, S, L, U, fusion)
     z_out = torch.empty((M, N, D), dtype=torch.float32, device=dev)
     sld = torch.empty((M, N), dtype=torch.float32, device=dev)
     if N == 0:
-        out = (z_out.to(home), sld.to(home))
+        out = _home((z_out, sld), home, dev)
         return out + (torch.empty((M, N), dtype=torch.float64, device=home),) if want_log_q else out
-    ws_bytes = check(lib.tnf_flow_workspace_bytes(M, N, D, S, L, U, fusion))
-    ws = _workspace(ws_bytes, dev)
+    ws, ws_bytes = _ws(check(lib.tnf_flow_workspace_bytes(M, N, D, S, L, U, fusion)), dev)
     log_q = None
     if want_log_q and fusion == _lib.FUSE_FLOW:
         log_q = torch.empty((M, N), dtype=torch.float64, device=dev)
         rc = lib.tnf_flow_forward_logq_f32(oc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
-                                           None if interval_consts is None else interval_consts.data_ptr(),
-                                           z_out.data_ptr(), sld.data_ptr(), log_q.data_ptr(), Mz, Mp, N, D, S, L, U,
-                                           pstride, fusion, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+                                           _ptr(interval_consts), z_out.data_ptr(), sld.data_ptr(), log_q.data_ptr(),
+                                           Mz, Mp, N, D, S, L, U, pstride, fusion, ws, ws_bytes, _lib.stream_ptr())
         if rc == _lib.EUNSUPPORTED:
             log_q = None  # a selectable variant without that output: the plain entry below, the caller adds the density
         else:
             check(rc)
     if log_q is None:
         check(lib.tnf_flow_forward_f32(oc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
-                                       None if interval_consts is None else interval_consts.data_ptr(),
-                                       z_out.data_ptr(), sld.data_ptr(), Mz, Mp, N, D, S, L, U, pstride,
-                                       fusion, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-    if home != dev:
-        z_out, sld = z_out.to(home), sld.to(home)
-        log_q = None if log_q is None else log_q.to(home)
-    return (z_out, sld, log_q) if want_log_q else (z_out, sld)
+                                       _ptr(interval_consts), z_out.data_ptr(), sld.data_ptr(), Mz, Mp, N, D, S, L, U,
+                                       pstride, fusion, ws, ws_bytes, _lib.stream_ptr()))
+    out = _home((z_out, sld, log_q), home, dev)
+    return out if want_log_q else out[:2]
 
 
 def flow_padded_supported(D, S, L, U):
@@ -596,39 +482,20 @@ def flow_padded_supported(D, S, L, U):
     return bool(lib.tnf_flow_padded_supported(D, S, L, U))
 
 
-def _padded_prep(z, params, bn_mean, bn_alpha):
-    _check3(z)
-    dev = _lib.require_device()
-    if z.dtype != torch.float32 or params.dtype != torch.float32:
-        raise TypeError("the fused flow kernels are float32")
-    zc = _stage(z, dev)  # rows of D floats; the kernel needs 4-byte alignment only, so a contiguous view is not copied
-    pc, pstride = _rows(params, dev)
-    return dev, zc, pc, pstride, _stats(bn_mean, dev), _stats(bn_alpha, dev)
-
-
 def flow_padded_log_prob_raw(z, params, bn_mean, bn_alpha, D, S, L, U, want_z0=False, want_sld=False, want_lp=True,
                              count_reruns=False):
     """tnf_flow_padded_log_prob_f32: flow_log_prob_raw on the padded whole-flow kernel (one launch, any
     2 <= D <= 63 but 32).  Returns (log_prob | None, z0 | None, sum_log_det | None) (+ the rerun counter, see
     flow_log_prob_raw)."""
-    home = z.device
-    dev, zc, pc, pstride, mean_c, alpha_c = _padded_prep(z, params, bn_mean, bn_alpha)
-    Mz, N = zc.shape[0], zc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
-    lp = torch.empty((M, N), dtype=torch.float32, device=dev) if want_lp else None
-    z0 = torch.empty((M, N, D), dtype=torch.float32, device=dev) if want_z0 else None
-    sld = torch.empty((M, N), dtype=torch.float32, device=dev) if want_sld else None
-    reruns = torch.zeros(1, dtype=torch.int32, device=dev) if count_reruns else None
+    dev, zc, pc, pstride, mean_c, alpha_c, Mz, Mp, M, N = _flow_prep(z, params, bn_mean, bn_alpha)
+    lp, z0, sld = _empty_f32(want_lp, (M, N), dev), _empty_f32(want_z0, (M, N, D), dev), _empty_f32(want_sld, (M, N), dev)
+    reruns = torch.zeros(1, dtype=torch.int32, device=dev) if count_reruns else None  # stays on the compute device
     if N > 0:
-        ws = _workspace(check(lib.tnf_flow_padded_workspace_bytes(M, N, D, S, L, U)), dev)
+        ws, ws_bytes = _ws(check(lib.tnf_flow_padded_workspace_bytes(M, N, D, S, L, U)), dev)
         check(lib.tnf_flow_padded_log_prob_f32(zc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
-                                               None if lp is None else lp.data_ptr(),
-                                               None if z0 is None else z0.data_ptr(),
-                                               None if sld is None else sld.data_ptr(), Mz, Mp, N, D, S, L, U, pstride,
-                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr(),
-                                               None if reruns is None else reruns.data_ptr()))
-    out = tuple(t.to(home) if t is not None else None for t in (lp, z0, sld))
+                                               _ptr(lp), _ptr(z0), _ptr(sld), Mz, Mp, N, D, S, L, U, pstride,
+                                               ws, ws_bytes, _lib.stream_ptr(), _ptr(reruns)))
+    out = _home((lp, z0, sld), z.device, dev)
     return out + (reruns,) if count_reruns else out
 
 
@@ -636,21 +503,16 @@ def flow_padded_forward_raw(omega, params, bn_mean, bn_alpha, D, S, L, U, want_l
     """tnf_flow_padded_forward_f32: flow_forward_raw (frozen BatchNorm) on the padded whole-flow kernel.
     Returns (z (M,N,D), sum_log_det (M,N)) and, with want_log_q, log_q (M,N) float64 = log N(omega) - sum_log_det
     written by the kernel."""
-    home = omega.device
-    dev, oc, pc, pstride, mean_c, alpha_c = _padded_prep(omega, params, bn_mean, bn_alpha)
-    Mz, N = oc.shape[0], oc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
+    dev, oc, pc, pstride, mean_c, alpha_c, Mz, Mp, M, N = _flow_prep(omega, params, bn_mean, bn_alpha)
     z_out = torch.empty((M, N, D), dtype=torch.float32, device=dev)
     sld = torch.empty((M, N), dtype=torch.float32, device=dev)
     log_q = torch.empty((M, N), dtype=torch.float64, device=dev) if want_log_q else None
     if N > 0:
-        ws = _workspace(check(lib.tnf_flow_padded_workspace_bytes(M, N, D, S, L, U)), dev)
+        ws, ws_bytes = _ws(check(lib.tnf_flow_padded_workspace_bytes(M, N, D, S, L, U)), dev)
         check(lib.tnf_flow_padded_forward_f32(oc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
-                                              z_out.data_ptr(), sld.data_ptr(), None if log_q is None else log_q.data_ptr(),
-                                              Mz, Mp, N, D, S, L, U, pstride, ws.data_ptr(), ws.numel(),
-                                              _lib.stream_ptr()))
-    out = tuple(t.to(home) if t is not None else None for t in (z_out, sld, log_q))
+                                              z_out.data_ptr(), sld.data_ptr(), _ptr(log_q), Mz, Mp, N, D, S, L, U,
+                                              pstride, ws, ws_bytes, _lib.stream_ptr()))
+    out = _home((z_out, sld, log_q), omega.device, dev)
     return out if want_log_q else out[:2]
 
 
@@ -658,6 +520,19 @@ def flow_padded_forward_raw(omega, params, bn_mean, bn_alpha, D, S, L, U, want_l
 # flow level, with autograd: log_prob through one fused kernel per layer, backward through one
 # MFMA backward kernel per layer (tnf_flow_log_prob_fwd_f32 / _bwd_f32)
 # ---------------------------------------------------------------------------
+def _batch_prep(omega, params, D, S):
+    """Inputs and outputs of a batch-statistics forward on the compute device
+    -> (dev, oc, pc, pstride, z, sld, bn_mean (2S, D), bn_alpha (2S, D))."""
+    dev = _lib.require_device()
+    oc = _stage(omega.detach(), dev)
+    pc, pstride = _rows(params.detach(), dev)
+    z = torch.empty_like(oc)
+    sld = torch.empty(oc.shape[:2], dtype=torch.float32, device=dev)
+    mean = torch.empty((2 * S, D), dtype=torch.float32, device=dev)
+    alpha = torch.empty((2 * S, D), dtype=torch.float32, device=dev)
+    return dev, oc, pc, pstride, z, sld, mean, alpha
+
+
 def flow_forward_batch_raw(omega, params, D, S, L, U, eps, reduce_moments=None):
     """tnf_flow_forward_batch_f32: NormFlow.forward with batch-statistics BatchNorm and no autograd in one call
     -> (z, sum_log_det, bn_mean (2S, D), bn_alpha (2S, D)), all on the compute device.
@@ -668,43 +543,29 @@ def flow_forward_batch_raw(omega, params, D, S, L, U, eps, reduce_moments=None):
     rank normalises with the statistics of the GLOBAL batch exactly as the single-device call would
     (bijectors.py:401-415).  The chain then runs in steps (tnf_flow_forward_batch_begin / _layer / _fold / _end_f32)
     with the collective on the same stream between a layer and its fold."""
-    dev = _lib.require_device()
-    oc = _stage(omega.detach(), dev)
-    pc, pstride = _rows(params.detach(), dev)
     if reduce_moments is not None:
-        return run_batch_steps(FlowForwardBatchSteps(oc, pc, D, S, L, U, eps), reduce_moments)
+        return run_batch_steps(FlowForwardBatchSteps(omega, params, D, S, L, U, eps), reduce_moments)
+    dev, oc, pc, pstride, z, sld, mean, alpha = _batch_prep(omega, params, D, S)
     M, N = oc.shape[0], oc.shape[1]
     Mp = pc.shape[0]
-    z = torch.empty_like(oc)
-    sld = torch.empty((M, N), dtype=torch.float32, device=dev)
-    mean = torch.empty((2 * S, D), dtype=torch.float32, device=dev)
-    alpha = torch.empty((2 * S, D), dtype=torch.float32, device=dev)
-    nbytes = check(lib.tnf_flow_forward_batch_workspace_bytes(Mp, D, S, L))
-    ws = _workspace(nbytes, dev)
+    ws, ws_bytes = _ws(check(lib.tnf_flow_forward_batch_workspace_bytes(Mp, D, S, L)), dev)
     check(lib.tnf_flow_forward_batch_f32(oc.data_ptr(), pc.data_ptr(), z.data_ptr(), sld.data_ptr(), mean.data_ptr(),
-                                         alpha.data_ptr(), M, Mp, N, D, S, L, U, pstride, float(eps), ws.data_ptr(),
-                                         nbytes, _lib.stream_ptr()))
-    return z, sld, mean, alpha
+                                         alpha.data_ptr(), M, Mp, N, D, S, L, U, pstride, float(eps), ws, ws_bytes,
+                                         _lib.stream_ptr()))
+    return z, sld, mean, alpha  # on the compute device: the caller carries on there
 
 
 class FlowForwardBatchSteps:
     """One rank's share of a batch-statistics forward, step by step (tnf_flow_forward_batch_begin / _layer / _fold /
     _end_f32): `layer(c)` returns this rank's moments of layer c's output, `fold(c)` consumes the moments AS THEY ARE
-    THEN (summed over the ranks by the caller) -- see run_batch_steps."""
+    THEN (summed over the ranks by the caller) -- see run_batch_steps.  Results stay on the compute device."""
 
     def __init__(self, omega, params, D, S, L, U, eps):
-        dev = _lib.require_device()
-        self.omega = _stage(omega.detach(), dev)
-        self.params, self.pstride = _rows(params.detach(), dev)
+        dev, self.omega, self.params, self.pstride, self.z, self.sld, self.mean, self.alpha = _batch_prep(omega, params, D, S)
         self.cfg = (D, S, L, U)
         self.eps = float(eps)
         self.n_layers = 2 * S
-        M, N = self.omega.shape[0], self.omega.shape[1]
-        self.M, self.N, self.Mp = M, N, self.params.shape[0]
-        self.z = torch.empty_like(self.omega)
-        self.sld = torch.empty((M, N), dtype=torch.float32, device=dev)
-        self.mean = torch.empty((2 * S, D), dtype=torch.float32, device=dev)
-        self.alpha = torch.empty((2 * S, D), dtype=torch.float32, device=dev)
+        self.M, self.N, self.Mp = self.omega.shape[0], self.omega.shape[1], self.params.shape[0]
         self.nbytes = check(lib.tnf_flow_forward_batch_workspace_bytes(self.Mp, D, S, L))
         # a workspace of its own: it must survive the collectives between the steps
         self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
@@ -752,27 +613,20 @@ def run_batch_steps(steps, reduce_moments=None):
 
 class _FlowForwardTrainFn(torch.autograd.Function):
     """NormFlow.forward with fresh batch statistics under autograd (tnf_flow_forward_train_fwd_f32 / _bwd_f32): one
-    node for the whole stack.  Returns (z, sum_log_det, bn_mean, bn_alpha); the statistics are not differentiable
-    outputs (the BatchNorm layers cache them detached, as everywhere in this package)."""
+    node for the whole stack.  Returns (z, sum_log_det, bn_mean, bn_alpha) on the compute device; the statistics are not
+    differentiable outputs (the BatchNorm layers cache them detached, as everywhere in this package)."""
 
     @_records_options
     def forward(ctx, omega, params, D, S, L, U, eps):
-        dev = _lib.require_device()
-        oc = _stage(omega.detach(), dev)
-        pc, pstride = _rows(params.detach(), dev)
+        dev, oc, pc, pstride, z, sld, mean, alpha = _batch_prep(omega, params, D, S)
         M, N = oc.shape[0], oc.shape[1]
         Mp = pc.shape[0]
-        z = torch.empty_like(oc)
-        sld = torch.empty((M, N), dtype=torch.float32, device=dev)
         states = torch.empty((2 * S, M, N, D), dtype=torch.float32, device=dev)
         folds = torch.empty((2 * S, Mp, 2, D), dtype=torch.float32, device=dev)
-        mean = torch.empty((2 * S, D), dtype=torch.float32, device=dev)
-        alpha = torch.empty((2 * S, D), dtype=torch.float32, device=dev)
-        nbytes = check(lib.tnf_flow_forward_train_workspace_bytes(M, Mp, N, D, S, L))
-        ws = _workspace(nbytes, dev)
+        ws, ws_bytes = _ws(check(lib.tnf_flow_forward_train_workspace_bytes(M, Mp, N, D, S, L)), dev)
         check(lib.tnf_flow_forward_train_fwd_f32(oc.data_ptr(), pc.data_ptr(), z.data_ptr(), sld.data_ptr(),
                                                  states.data_ptr(), folds.data_ptr(), mean.data_ptr(), alpha.data_ptr(),
-                                                 M, Mp, N, D, S, L, U, pstride, float(eps), ws.data_ptr(), nbytes,
+                                                 M, Mp, N, D, S, L, U, pstride, float(eps), ws, ws_bytes,
                                                  _lib.stream_ptr()))
         ctx.save_for_backward(oc, pc, states, folds, mean, alpha)
         ctx.cfg = (D, S, L, U, pstride, omega.device, params.device, tuple(params.shape))
@@ -790,15 +644,12 @@ class _FlowForwardTrainFn(torch.autograd.Function):
         gs = _stage(_grad_or_zeros(g_sld, (M, N), torch.float32, dev).float(), dev)
         go = torch.empty_like(oc) if ctx.needs_input_grad[0] else None
         gp = torch.zeros(p_shape, dtype=torch.float32, device=dev)
-        nbytes = check(lib.tnf_flow_forward_train_workspace_bytes(M, Mp, N, D, S, L))
-        ws = _workspace(nbytes, dev)
+        ws, ws_bytes = _ws(check(lib.tnf_flow_forward_train_workspace_bytes(M, Mp, N, D, S, L)), dev)
         check(lib.tnf_flow_forward_train_bwd_f32(oc.data_ptr(), pc.data_ptr(), states.data_ptr(), folds.data_ptr(),
                                                  mean.data_ptr(), alpha.data_ptr(), gz.data_ptr(), gs.data_ptr(),
-                                                 go.data_ptr() if go is not None else None, gp.data_ptr(), M, Mp, N, D, S,
-                                                 L, U, pstride, gp.shape[1], ws.data_ptr(), nbytes, _lib.stream_ptr()))
-        if go is not None and o_home != dev:
-            go = go.to(o_home)
-        return go, (gp if p_home == dev else gp.to(p_home)), None, None, None, None, None
+                                                 _ptr(go), gp.data_ptr(), M, Mp, N, D, S,
+                                                 L, U, pstride, gp.shape[1], ws, ws_bytes, _lib.stream_ptr()))
+        return _home(go, o_home, dev), _home(gp, p_home, dev), None, None, None, None, None
 
 
 def flow_forward_train(omega, params, D, S, L, U, eps):
@@ -809,44 +660,59 @@ def flow_train_supported(M, Mp, N, D, S, L, U):
     return Mp in (1, M) and N >= 32 and lib.tnf_flow_train_workspace_bytes(M, Mp, max(N, 1), D, S, L, U) >= 0
 
 
+def _train_prep(z, params, bn_mean, bn_alpha):
+    """What a log_prob training forward stages -> (dev, zc, pc, pstride, mean_c, alpha_c); its callers
+    (flow_train_supported / flow_train_rev_supported) have settled how the batches match."""
+    dev = _lib.require_device()
+    pc, pstride = _rows(params.detach(), dev)
+    return dev, _stage(z.detach(), dev), pc, pstride, _stats(bn_mean, dev), _stats(bn_alpha, dev)
+
+
+def _layer_pair_ws(zc, pc, D, S, L, U):
+    """The workspace of the per-layer training pair, (pointer, size)."""
+    return _ws(check(lib.tnf_flow_train_workspace_bytes(zc.shape[0], pc.shape[0], zc.shape[1], D, S, L, U)), zc.device)
+
+
+def _layer_pair_fwd(zc, pc, pstride, mean_c, alpha_c, D, S, L, U, ws):
+    """tnf_flow_log_prob_fwd_f32 on staged operands -> (log_prob, the 2S - 1 kept layer inputs)."""
+    M, N = zc.shape[0], zc.shape[1]
+    lp = torch.empty((M, N), dtype=torch.float32, device=zc.device)
+    states = torch.empty((2 * S - 1, M, N, D), dtype=torch.float32, device=zc.device)
+    check(lib.tnf_flow_log_prob_fwd_f32(zc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
+                                        lp.data_ptr(), states.data_ptr(), M, pc.shape[0], N, D, S, L, U, pstride,
+                                        *ws, _lib.stream_ptr()))
+    return lp, states
+
+
+def _layer_pair_bwd(zc, states, pc, pstride, mean_c, alpha_c, g, D, S, L, U, p_shape, ws):
+    """tnf_flow_log_prob_bwd_f32 on staged operands -> (g_z, g_params) on the compute device."""
+    gz = torch.empty_like(zc)
+    gp = torch.zeros(p_shape, dtype=torch.float32, device=zc.device)
+    check(lib.tnf_flow_log_prob_bwd_f32(zc.data_ptr(), states.data_ptr(), pc.data_ptr(), mean_c.data_ptr(),
+                                        alpha_c.data_ptr(), g.data_ptr(), gz.data_ptr(), gp.data_ptr(), zc.shape[0],
+                                        pc.shape[0], zc.shape[1], D, S, L, U, pstride, gp.shape[1], *ws,
+                                        _lib.stream_ptr()))
+    return gz, gp
+
+
 class _FlowLogProbFn(torch.autograd.Function):
     @_records_options
     def forward(ctx, z, params, bn_mean, bn_alpha, D, S, L, U):
-        dev = _lib.require_device()
-        zc = _stage(z.detach(), dev)
-        pc, pstride = _rows(params.detach(), dev)
-        mean_c, alpha_c = _stats(bn_mean, dev), _stats(bn_alpha, dev)
-        M, N = zc.shape[0], zc.shape[1]
-        Mp = pc.shape[0]
-        lp = torch.empty((M, N), dtype=torch.float32, device=dev)
-        states = torch.empty((2 * S - 1, M, N, D), dtype=torch.float32, device=dev)
-        ws_bytes = check(lib.tnf_flow_train_workspace_bytes(M, Mp, N, D, S, L, U))
-        ws = _workspace(ws_bytes, dev)
-        check(lib.tnf_flow_log_prob_fwd_f32(zc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
-                                            lp.data_ptr(), states.data_ptr(), M, Mp, N, D, S, L, U, pstride,
-                                            ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        dev, zc, pc, pstride, mean_c, alpha_c = _train_prep(z, params, bn_mean, bn_alpha)
+        lp, states = _layer_pair_fwd(zc, pc, pstride, mean_c, alpha_c, D, S, L, U, _layer_pair_ws(zc, pc, D, S, L, U))
         ctx.save_for_backward(zc, pc, mean_c, alpha_c, states)
         ctx.cfg = (D, S, L, U, pstride, z.device, params.device, tuple(params.shape))
-        return lp if z.device == dev else lp.to(z.device)
+        return _home(lp, z.device, dev)
 
     @_reenters_options
     def backward(ctx, g_lp):
         zc, pc, mean_c, alpha_c, states = ctx.saved_tensors
         D, S, L, U, pstride, z_home, p_home, p_shape = ctx.cfg
         dev = zc.device
-        M, N = zc.shape[0], zc.shape[1]
-        Mp = pc.shape[0]
         g = _stage(g_lp.float(), dev)
-        gz = torch.empty_like(zc)
-        gp = torch.zeros(p_shape, dtype=torch.float32, device=dev)
-        ws_bytes = check(lib.tnf_flow_train_workspace_bytes(M, Mp, N, D, S, L, U))
-        ws = _workspace(ws_bytes, dev)
-        check(lib.tnf_flow_log_prob_bwd_f32(zc.data_ptr(), states.data_ptr(), pc.data_ptr(), mean_c.data_ptr(),
-                                            alpha_c.data_ptr(), g.data_ptr(), gz.data_ptr(), gp.data_ptr(), M, Mp,
-                                            N, D, S, L, U, pstride, gp.shape[1], ws.data_ptr(), ws.numel(),
-                                            _lib.stream_ptr()))
-        return (gz if z_home == dev else gz.to(z_home)), (gp if p_home == dev else gp.to(p_home)), None, None, \
-            None, None, None, None
+        gz, gp = _layer_pair_bwd(zc, states, pc, pstride, mean_c, alpha_c, g, D, S, L, U, p_shape,
+                                 _layer_pair_ws(zc, pc, D, S, L, U))
+        return _home(gz, z_home, dev), _home(gp, p_home, dev), None, None, None, None, None, None
 
 
 def flow_train_rev_supported(M, Mp, N, D, S, L, U):
@@ -881,10 +747,7 @@ class _FlowLogProbRevFn(torch.autograd.Function):
 
     @_records_options
     def forward(ctx, z, params, bn_mean, bn_alpha, D, S, L, U):
-        dev = _lib.require_device()
-        zc = _stage(z.detach(), dev)
-        pc, pstride = _rows(params.detach(), dev)
-        mean_c, alpha_c = _stats(bn_mean, dev), _stats(bn_alpha, dev)
+        dev, zc, pc, pstride, mean_c, alpha_c = _train_prep(z, params, bn_mean, bn_alpha)
         M, N = zc.shape[0], zc.shape[1]
         Mp = pc.shape[0]
         lp = torch.empty((M, N), dtype=torch.float32, device=dev)
@@ -894,7 +757,7 @@ class _FlowLogProbRevFn(torch.autograd.Function):
                                                 _lib.stream_ptr()))
         ctx.save_for_backward(z0, pc, mean_c, alpha_c, zc)  # zc: the caller's tensor (no copy), for the fallback only
         ctx.cfg = (D, S, L, U, pstride, z.device, params.device, tuple(params.shape))
-        return lp if z.device == dev else lp.to(z.device)
+        return _home(lp, z.device, dev)
 
     @_reenters_options
     def backward(ctx, g_lp):
@@ -906,8 +769,7 @@ class _FlowLogProbRevFn(torch.autograd.Function):
         g = _stage(g_lp.float(), dev)
         gz = torch.empty_like(z0) if ctx.needs_input_grad[0] else None
         gp = torch.zeros(p_shape, dtype=torch.float32, device=dev)
-        ws_bytes = check(lib.tnf_flow_train_rev_workspace_bytes(M, Mp, N, D, S, L, U))
-        ws = _workspace(ws_bytes, dev)
+        ws, ws_bytes = _ws(check(lib.tnf_flow_train_rev_workspace_bytes(M, Mp, N, D, S, L, U)), dev)
         mode = _FlowLogProbRevFn.overflow_recovery if _FlowLogProbRevFn.check_overflow else "off"
         if mode != "off" and not flow_train_supported(M, Mp, N, D, S, L, U):
             mode = "off"  # no per-layer pair for this shape: the poison is all there is
@@ -915,10 +777,8 @@ class _FlowLogProbRevFn(torch.autograd.Function):
             mode = "off"
         flag = torch.zeros(1, dtype=torch.int32, device=dev) if mode != "off" else None
         check(lib.tnf_flow_log_prob_bwd_rev_f32(z0.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
-                                                g.data_ptr(), gz.data_ptr() if gz is not None else None,
-                                                gp.data_ptr(), M, Mp, N, D, S, L, U, pstride, gp.shape[1],
-                                                ws.data_ptr(), ws.numel(), None if flag is None else flag.data_ptr(),
-                                                _lib.stream_ptr()))
+                                                g.data_ptr(), _ptr(gz), gp.data_ptr(), M, Mp, N, D, S, L, U, pstride,
+                                                gp.shape[1], ws, ws_bytes, _ptr(flag), _lib.stream_ptr()))
         if mode == "host" and int(flag.item()) != 0:
             # a term left the fixed-point budget: the same step through the per-layer pair, fp32 layer kernels
             _FlowLogProbRevFn.overflow_fallbacks += 1
@@ -937,33 +797,15 @@ class _FlowLogProbRevFn(torch.autograd.Function):
             check(lib.tnf_gated_copy_f32(flag.data_ptr(), gp.data_ptr(), gp2.data_ptr(), gp.numel(), _lib.stream_ptr()))
             if gz is not None:
                 check(lib.tnf_gated_copy_f32(flag.data_ptr(), gz.data_ptr(), gz2.data_ptr(), gz.numel(), _lib.stream_ptr()))
-        if gz is not None and z_home != dev:
-            gz = gz.to(z_home)
-        return gz, (gp if p_home == dev else gp.to(p_home)), None, None, None, None, None, None
+        return _home(gz, z_home, dev), _home(gp, p_home, dev), None, None, None, None, None, None
 
 
 def _flow_log_prob_grad_fp32(zc, pc, pstride, mean_c, alpha_c, g, D, S, L, U, p_shape, want_gz):
     """Gradient of log_prob w.r.t. (z, params) through the per-layer training pair with the fp32-MFMA layer backward."""
-    dev = zc.device
-    M, N = zc.shape[0], zc.shape[1]
-    Mp = pc.shape[0]
-    lp = torch.empty((M, N), dtype=torch.float32, device=dev)
-    states = torch.empty((2 * S - 1, M, N, D), dtype=torch.float32, device=dev)
-    ws_bytes = check(lib.tnf_flow_train_workspace_bytes(M, Mp, N, D, S, L, U))
-    ws = _workspace(ws_bytes, dev)
-    check(lib.tnf_flow_log_prob_fwd_f32(zc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(), lp.data_ptr(),
-                                        states.data_ptr(), M, Mp, N, D, S, L, U, pstride, ws.data_ptr(), ws.numel(),
-                                        _lib.stream_ptr()))
-    gz = torch.empty_like(zc)
-    gp = torch.zeros(p_shape, dtype=torch.float32, device=dev)
-    before = _lib.options_snapshot()
-    check(lib.tnf_set_option(_lib.OPT_TRAIN_BWD_FP32, 1))
-    try:
-        check(lib.tnf_flow_log_prob_bwd_f32(zc.data_ptr(), states.data_ptr(), pc.data_ptr(), mean_c.data_ptr(),
-                                            alpha_c.data_ptr(), g.data_ptr(), gz.data_ptr(), gp.data_ptr(), M, Mp, N, D, S,
-                                            L, U, pstride, gp.shape[1], ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-    finally:
-        check(lib.tnf_set_option(_lib.OPT_TRAIN_BWD_FP32, before[_lib._OPTION_KEYS.index(_lib.OPT_TRAIN_BWD_FP32)]))
+    ws = _layer_pair_ws(zc, pc, D, S, L, U)
+    _lp, states = _layer_pair_fwd(zc, pc, pstride, mean_c, alpha_c, D, S, L, U, ws)
+    with _lib.option_set(_lib.OPT_TRAIN_BWD_FP32, 1):
+        gz, gp = _layer_pair_bwd(zc, states, pc, pstride, mean_c, alpha_c, g, D, S, L, U, p_shape, ws)
     return (gz if want_gz else None), gp
 
 
@@ -981,44 +823,29 @@ def maf_raw(z, params, masks, D, L, U, inverse):
     """tnf_maf.  masks: 1-D tensor (the layer masks concatenated).  Returns (z_out, log_det (M,N))."""
     _check3(z)
     dev = _lib.require_device()
-    home = z.device
     code = _dtype_code(z)
-    if params.dtype != z.dtype:
-        raise TypeError("z (%s) and params (%s) must have the same dtype" % (z.dtype, params.dtype))
-    zc = _stage(z, dev)
-    pc, pstride = _rows(params, dev)
-    mk = masks if (masks.device == dev and masks.dtype == z.dtype) else _stage(masks.to(z.dtype), dev)
-    Mz, N = zc.shape[0], zc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
-    if zc.shape[2] != D:
-        raise ValueError("last dimension of z (%d) must equal D (%d)" % (zc.shape[2], D))
+    zc, pc, pstride, Mz, Mp, M, N = _pair(z, params, dev, D, same_dtype=True)
+    mk = _masks(masks, z.dtype, dev)
     z_out = torch.empty((M, N, D), dtype=z.dtype, device=dev)
     log_det = torch.empty((M, N), dtype=z.dtype, device=dev)
     if N > 0:
         check(lib.tnf_maf(code, zc.data_ptr(), pc.data_ptr(), mk.data_ptr(), z_out.data_ptr(), log_det.data_ptr(),
                           Mz, Mp, N, D, L, U, int(inverse), pstride, _lib.stream_ptr()))
-    if home != dev:
-        z_out, log_det = z_out.to(home), log_det.to(home)
-    return z_out, log_det
+    return _home((z_out, log_det), z.device, dev)
 
 
 def maf_inverse_alpha_raw(x, params, masks, D, L, U):
     """tnf_maf_inverse_alpha: per-dimension f_alpha(x) (M, N, D) of MAF.inverse_and_log_det on the compute device."""
     dev = _lib.require_device()
-    xc = _stage(x, dev)
-    pc, pstride = _rows(params, dev)
-    mk = masks if (masks.device == dev and masks.dtype == x.dtype) else _stage(masks.to(x.dtype), dev)
-    Mz, N = xc.shape[0], xc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
+    xc, pc, pstride, Mz, Mp, M, N = _pair(x, params, dev)
+    mk = _masks(masks, x.dtype, dev)
     out = torch.empty((M, N, D), dtype=x.dtype, device=dev)
     ld = torch.empty((M, N), dtype=x.dtype, device=dev)
     alpha = torch.empty((M, N, D), dtype=x.dtype, device=dev)
     if N > 0:
         check(lib.tnf_maf_inverse_alpha(_dtype_code(x), xc.data_ptr(), pc.data_ptr(), mk.data_ptr(), out.data_ptr(),
                                         ld.data_ptr(), alpha.data_ptr(), Mz, Mp, N, D, L, U, pstride, _lib.stream_ptr()))
-    return alpha
+    return alpha  # on the compute device: _MafFn's backward carries on there
 
 
 class _MafFn(torch.autograd.Function):
@@ -1080,17 +907,10 @@ def maf(z, params, masks, D, L, U, inverse):
 # ---------------------------------------------------------------------------
 # Support layers (ToInterval / ToSimplex): parameter-free, elementwise + per-row log-det
 # ---------------------------------------------------------------------------
-def _grad_or_zeros(g, shape, dtype, dev):
-    if g is None:
-        return torch.zeros(shape, dtype=dtype, device=dev)
-    return _stage(g, dev)
-
-
 def to_interval_raw(z, consts, inverse):
     """tnf_to_interval.  consts: (7, D) float32 rows (see include/tnf.h).  Returns (z_out, log_det (M,N))."""
     _check3(z)
     dev = _lib.require_device()
-    home = z.device
     code = _dtype_code(z)
     zc = _stage(z, dev)
     cc = _stats(consts, dev)
@@ -1101,9 +921,7 @@ def to_interval_raw(z, consts, inverse):
     log_det = torch.empty((M, N), dtype=z.dtype, device=dev)
     check(lib.tnf_to_interval(code, zc.data_ptr(), cc.data_ptr(), z_out.data_ptr(), log_det.data_ptr(), M * N, D,
                               int(inverse), _lib.stream_ptr()))
-    if home != dev:
-        z_out, log_det = z_out.to(home), log_det.to(home)
-    return z_out, log_det
+    return _home((z_out, log_det), z.device, dev)
 
 
 class _ToIntervalFn(torch.autograd.Function):
@@ -1126,7 +944,7 @@ class _ToIntervalFn(torch.autograd.Function):
         check(lib.tnf_to_interval_backward(_dtype_code(z), zc.data_ptr(), _stats(consts, dev).data_ptr(),
                                            g_zo.data_ptr(), g_l.data_ptr(), gz.data_ptr(), M * N, D,
                                            int(ctx.inverse), _lib.stream_ptr()))
-        return (gz if z.device == dev else gz.to(z.device)), None, None
+        return _home(gz, z.device, dev), None, None
 
 
 def to_interval(z, consts, inverse):
@@ -1139,7 +957,6 @@ def to_simplex_raw(z, D_attr):
     """tnf_to_simplex: (M, N, D_in) -> ((M, N, D_in + 1), log_det (M, N))."""
     _check3(z)
     dev = _lib.require_device()
-    home = z.device
     code = _dtype_code(z)
     zc = _stage(z, dev)
     M, N, Din = zc.shape
@@ -1147,9 +964,7 @@ def to_simplex_raw(z, D_attr):
     log_det = torch.empty((M, N), dtype=z.dtype, device=dev)
     check(lib.tnf_to_simplex(code, zc.data_ptr(), z_out.data_ptr(), log_det.data_ptr(), M * N, Din, D_attr,
                              _lib.stream_ptr()))
-    if home != dev:
-        z_out, log_det = z_out.to(home), log_det.to(home)
-    return z_out, log_det
+    return _home((z_out, log_det), z.device, dev)
 
 
 class _ToSimplexFn(torch.autograd.Function):
@@ -1171,7 +986,7 @@ class _ToSimplexFn(torch.autograd.Function):
         gz = torch.empty_like(zc)
         check(lib.tnf_to_simplex_backward(_dtype_code(z), zc.data_ptr(), g_zo.data_ptr(), g_l.data_ptr(),
                                           gz.data_ptr(), M * N, Din, ctx.D_attr, _lib.stream_ptr()))
-        return (gz if z.device == dev else gz.to(z.device)), None
+        return _home(gz, z.device, dev), None
 
 
 def to_simplex(z, D_attr):
@@ -1194,13 +1009,12 @@ def ef_suffstats_raw(z, family):
     """tnf_ef_suffstats: (M, N, D) -> T(z) (M, N, D_eta), on z's device."""
     _check3(z)
     dev = _lib.require_device()
-    home = z.device
     code = _dtype_code(z)
     zc = _stage(z, dev)
     M, N, D = zc.shape
     out = torch.empty((M, N, ef_num_eta(family, D)), dtype=z.dtype, device=dev)
     check(lib.tnf_ef_suffstats(code, family, zc.data_ptr(), out.data_ptr(), M * N, D, _lib.stream_ptr()))
-    return out if home == dev else out.to(home)
+    return _home(out, z.device, dev)
 
 
 class _EfSuffstatsFn(torch.autograd.Function):
@@ -1221,7 +1035,7 @@ class _EfSuffstatsFn(torch.autograd.Function):
         gz = torch.empty_like(zc)
         check(lib.tnf_ef_suffstats_backward(_dtype_code(z), ctx.family, zc.data_ptr(), g.data_ptr(), gz.data_ptr(), M * N,
                                             D, _lib.stream_ptr()))
-        return (gz if z.device == dev else gz.to(z.device)), None
+        return _home(gz, z.device, dev), None
 
 
 def ef_suffstats(z, family):
@@ -1247,14 +1061,13 @@ def ef_dot_raw(z, eta, family):
     """tnf_ef_dot: out[m, n] = eta[m] . T(z[m, n]) without forming T(z).  Returns (M, N) on z's device."""
     _ef_dot_check(z, eta, family)
     dev = _lib.require_device()
-    home = z.device
     code = _dtype_code(z)
     zc = _stage(z, dev)
     ec, ld_eta = _rows(eta, dev)
     M, N, D = zc.shape
     out = torch.empty((M, N), dtype=z.dtype, device=dev)
     check(lib.tnf_ef_dot(code, family, zc.data_ptr(), ec.data_ptr(), out.data_ptr(), M, N, D, ld_eta, _lib.stream_ptr()))
-    return out if home == dev else out.to(home)
+    return _home(out, z.device, dev)
 
 
 class _EfDotFn(torch.autograd.Function):
@@ -1276,20 +1089,12 @@ class _EfDotFn(torch.autograd.Function):
         want_z, want_eta = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         gz = torch.empty_like(zc) if want_z else None
         ge = torch.empty((M, eta.shape[1]), dtype=z.dtype, device=dev) if want_eta else None
-        ws, need = None, 0
+        ws, ws_bytes = None, 0  # the eta gradient alone is reduced through a workspace
         if want_eta:
-            need = lib.tnf_ef_dot_bwd_workspace_bytes(ctx.family, M, N, D)
-            check(need)
-            ws = _workspace(need, dev)
+            ws, ws_bytes = _ws(check(lib.tnf_ef_dot_bwd_workspace_bytes(ctx.family, M, N, D)), dev)
         check(lib.tnf_ef_dot_backward(_dtype_code(z), ctx.family, zc.data_ptr(), ec.data_ptr(), g.data_ptr(),
-                                      gz.data_ptr() if want_z else None, ge.data_ptr() if want_eta else None, M, N, D,
-                                      ld_eta, ws.data_ptr() if want_eta else None, ws.numel() if want_eta else 0,
-                                      _lib.stream_ptr()))
-        if want_z and z.device != dev:
-            gz = gz.to(z.device)
-        if want_eta and eta.device != dev:
-            ge = ge.to(eta.device)
-        return gz, ge, None
+                                      _ptr(gz), _ptr(ge), M, N, D, ld_eta, ws, ws_bytes, _lib.stream_ptr()))
+        return _home(gz, z.device, dev), _home(ge, eta.device, dev), None
 
 
 def ef_dot(z, eta, family):
@@ -1320,9 +1125,9 @@ def _pad_cols(t, width):
     return t.contiguous()
 
 
-def cond_flow_log_prob_raw(z, h, weight, bias, bn_mean, bn_alpha, D, S, L, U, want_z0=False, want_sld=False):
-    """tnf_cond_flow_log_prob_f32: z (M, D), h (M, H) = input of param_net's last Linear, weight
-    (D_params, H) / bias (D_params) of that Linear.  Returns (log_prob (M), z0 | None, sum_log_det | None)."""
+def _cond_prep(what, z, h, weight, bias, bn_mean, bn_alpha, D):
+    """What the fused conditioner + flow entries stage: z (M, D), h (M, H) and the last Linear padded to the kernel's
+    width Hp -> (dev, M, H, Hp, zc, hc, wc, bc, mean, alpha).  Their results stay on the compute device."""
     dev = _lib.require_device()
     M, H = h.shape
     Hp = _cond_width(H)
@@ -1330,51 +1135,40 @@ def cond_flow_log_prob_raw(z, h, weight, bias, bn_mean, bn_alpha, D, S, L, U, wa
         raise ValueError("conditioner width %d not supported by the fused kernel (max 128)" % H)
     zc = _stage(z.detach().float(), dev)
     if zc.shape != (M, D):
-        raise ValueError("z must be (M, D) = (%d, %d), got %s" % (M, D, tuple(zc.shape)))
-    hc = _pad_cols(_stage(h, dev), Hp)
-    wc = _pad_cols(_stage(weight, dev), Hp)
+        raise ValueError("%s must be (M, D) = (%d, %d), got %s" % (what, M, D, tuple(zc.shape)))
+    hc = _pad_cols(_stage(h.detach(), dev), Hp)
+    wc = _pad_cols(_stage(weight.detach(), dev), Hp)
     bc = _stage(bias.detach().float(), dev)
-    mean = _stats(bn_mean, dev)
-    alpha = _stats(bn_alpha, dev)
+    return dev, M, H, Hp, zc, hc, wc, bc, _stats(bn_mean, dev), _stats(bn_alpha, dev)
+
+
+def cond_flow_log_prob_raw(z, h, weight, bias, bn_mean, bn_alpha, D, S, L, U, want_z0=False, want_sld=False):
+    """tnf_cond_flow_log_prob_f32: z (M, D), h (M, H) = input of param_net's last Linear, weight
+    (D_params, H) / bias (D_params) of that Linear.  Returns (log_prob (M), z0 | None, sum_log_det | None)."""
+    dev, M, H, Hp, zc, hc, wc, bc, mean, alpha = _cond_prep("z", z, h, weight, bias, bn_mean, bn_alpha, D)
     lp = torch.empty((M,), dtype=torch.float32, device=dev)
-    z0 = torch.empty((M, D), dtype=torch.float32, device=dev) if want_z0 else None
-    sld = torch.empty((M,), dtype=torch.float32, device=dev) if want_sld else None
-    nbytes = check(lib.tnf_cond_flow_workspace_bytes(D, S, L, U, Hp))
-    ws = _workspace(nbytes, dev)
+    z0, sld = _empty_f32(want_z0, (M, D), dev), _empty_f32(want_sld, (M,), dev)
+    ws, ws_bytes = _ws(check(lib.tnf_cond_flow_workspace_bytes(D, S, L, U, Hp)), dev)
     if M > 0:
         check(lib.tnf_cond_flow_log_prob_f32(zc.data_ptr(), hc.data_ptr(), wc.data_ptr(), bc.data_ptr(),
-                                             mean.data_ptr(), alpha.data_ptr(), lp.data_ptr(),
-                                             z0.data_ptr() if want_z0 else None,
-                                             sld.data_ptr() if want_sld else None, M, D, S, L, U, Hp,
-                                             hc.stride(0), wc.stride(0), ws.data_ptr(), nbytes, _lib.stream_ptr()))
-    return lp, z0, sld
+                                             mean.data_ptr(), alpha.data_ptr(), lp.data_ptr(), _ptr(z0), _ptr(sld),
+                                             M, D, S, L, U, Hp, hc.stride(0), wc.stride(0), ws, ws_bytes,
+                                             _lib.stream_ptr()))
+    return lp, z0, sld  # on the compute device
 
 
 def cond_flow_forward_raw(omega, h, weight, bias, bn_mean, bn_alpha, D, S, L, U):
     """tnf_cond_flow_forward_f32: omega (M, D) base draws, h (M, H) = input of param_net's last Linear, weight
     (D_params, H) / bias (D_params) of that Linear.  Returns (z (M, D), sum_log_det (M)); params never exist."""
-    dev = _lib.require_device()
-    M, H = h.shape
-    Hp = _cond_width(H)
-    if not Hp:
-        raise ValueError("conditioner width %d not supported by the fused kernel (max 128)" % H)
-    oc = _stage(omega.detach().float(), dev)
-    if oc.shape != (M, D):
-        raise ValueError("omega must be (M, D) = (%d, %d), got %s" % (M, D, tuple(oc.shape)))
-    hc = _pad_cols(_stage(h.detach(), dev), Hp)
-    wc = _pad_cols(_stage(weight.detach(), dev), Hp)
-    bc = _stage(bias.detach().float(), dev)
-    mean = _stats(bn_mean, dev)
-    alpha = _stats(bn_alpha, dev)
+    dev, M, H, Hp, oc, hc, wc, bc, mean, alpha = _cond_prep("omega", omega, h, weight, bias, bn_mean, bn_alpha, D)
     z = torch.empty((M, D), dtype=torch.float32, device=dev)
     sld = torch.empty((M,), dtype=torch.float32, device=dev)
-    nbytes = check(lib.tnf_cond_flow_workspace_bytes(D, S, L, U, Hp))
-    ws = _workspace(nbytes, dev)
+    ws, ws_bytes = _ws(check(lib.tnf_cond_flow_workspace_bytes(D, S, L, U, Hp)), dev)
     if M > 0:
         check(lib.tnf_cond_flow_forward_f32(oc.data_ptr(), hc.data_ptr(), wc.data_ptr(), bc.data_ptr(), mean.data_ptr(),
                                             alpha.data_ptr(), z.data_ptr(), sld.data_ptr(), M, D, S, L, U, Hp,
-                                            hc.stride(0), wc.stride(0), ws.data_ptr(), nbytes, _lib.stream_ptr()))
-    return z, sld
+                                            hc.stride(0), wc.stride(0), ws, ws_bytes, _lib.stream_ptr()))
+    return z, sld  # on the compute device
 
 
 class _CondFlowLogProbFn(torch.autograd.Function):
@@ -1384,27 +1178,19 @@ class _CondFlowLogProbFn(torch.autograd.Function):
 
     @_records_options
     def forward(ctx, z, h, weight, bias, bn_mean, bn_alpha, D, S, L, U):
-        dev = _lib.require_device()
-        M, H = h.shape
-        Hp = _cond_width(H)
-        zc = _stage(z.detach().float(), dev)
-        hc = _pad_cols(_stage(h, dev), Hp)
-        wc = _pad_cols(_stage(weight, dev), Hp)
-        bc = _stage(bias.detach().float(), dev)
-        mean, alpha = _stats(bn_mean, dev), _stats(bn_alpha, dev)
+        dev, M, H, Hp, zc, hc, wc, bc, mean, alpha = _cond_prep("z", z, h, weight, bias, bn_mean, bn_alpha, D)
         lp = torch.empty((M,), dtype=torch.float32, device=dev)
         acts = torch.empty((max(1, check(lib.tnf_cond_flow_acts_floats(M, D, S, L))),), dtype=torch.float32, device=dev)
-        nbytes = check(lib.tnf_cond_flow_workspace_bytes(D, S, L, U, Hp))
-        ws = _workspace(nbytes, dev)
+        ws, ws_bytes = _ws(check(lib.tnf_cond_flow_workspace_bytes(D, S, L, U, Hp)), dev)
         if M > 0:
             check(lib.tnf_cond_flow_log_prob_fwd_f32(zc.data_ptr(), hc.data_ptr(), wc.data_ptr(), bc.data_ptr(),
                                                      mean.data_ptr(), alpha.data_ptr(), lp.data_ptr(),
                                                      acts.data_ptr(), M, D, S, L, U, Hp, hc.stride(0), wc.stride(0),
-                                                     ws.data_ptr(), nbytes, _lib.stream_ptr()))
+                                                     ws, ws_bytes, _lib.stream_ptr()))
         ctx.save_for_backward(hc, wc, bc, mean, alpha, acts)
         ctx.cfg = (M, H, Hp, D, S, L, U)
         ctx.homes = (z.device, h.device, weight.device, bias.device)
-        return lp
+        return lp  # on the compute device
 
     @_reenters_options
     def backward(ctx, g_lp):
@@ -1412,25 +1198,22 @@ class _CondFlowLogProbFn(torch.autograd.Function):
         M, H, Hp, D, S, L, U = ctx.cfg
         dev = hc.device
         P = wc.shape[0]
-        need_z = ctx.needs_input_grad[0]
         g = _stage(g_lp.detach().float(), dev)
         g_h = torch.zeros((M, Hp), dtype=torch.float32, device=dev)
         g_w = torch.empty((P, Hp), dtype=torch.float32, device=dev)
         g_b = torch.empty((P,), dtype=torch.float32, device=dev)
-        g_z = torch.zeros((M, D), dtype=torch.float32, device=dev) if need_z else None
+        g_z = torch.zeros((M, D), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         deltas = torch.empty((max(1, check(lib.tnf_cond_flow_deltas_floats(M, D, S, L, Hp))),), dtype=torch.float32,
                              device=dev)
-        nbytes = check(lib.tnf_cond_flow_bwd_workspace_bytes(D, S, L, U, Hp))
-        ws = _workspace(nbytes, dev)
+        ws, ws_bytes = _ws(check(lib.tnf_cond_flow_bwd_workspace_bytes(D, S, L, U, Hp)), dev)
         check(lib.tnf_cond_flow_log_prob_bwd_f32(g.data_ptr(), hc.data_ptr(), wc.data_ptr(), bc.data_ptr(),
                                                  mean.data_ptr(), alpha.data_ptr(), acts.data_ptr(),
                                                  deltas.data_ptr(), g_h.data_ptr(), g_w.data_ptr(), g_b.data_ptr(),
-                                                 g_z.data_ptr() if need_z else None, M, D, S, L, U, Hp,
-                                                 hc.stride(0), wc.stride(0), g_h.stride(0), g_w.stride(0),
-                                                 ws.data_ptr(), nbytes, _lib.stream_ptr()))
+                                                 _ptr(g_z), M, D, S, L, U, Hp, hc.stride(0), wc.stride(0), g_h.stride(0),
+                                                 g_w.stride(0), ws, ws_bytes, _lib.stream_ptr()))
         hz, hh, hw, hb = ctx.homes
-        out_z = g_z.to(hz) if need_z else None
-        return (out_z, g_h[:, :H].to(hh), g_w[:, :H].to(hw), g_b.to(hb), None, None, None, None, None, None)
+        return (_home(g_z, hz, dev), _home(g_h[:, :H], hh, dev), _home(g_w[:, :H], hw, dev), _home(g_b, hb, dev),
+                None, None, None, None, None, None)
 
 
 def cond_flow_log_prob_train(z, h, weight, bias, bn_mean, bn_alpha, D, S, L, U):
@@ -1444,39 +1227,26 @@ def ar_flow_supported(D, L, U):
     return bool(lib.tnf_ar_flow_supported(D, L, U))
 
 
-def _ar_common(z, params, masks, bn_mean, bn_alpha, D):
+def _ar_prep(z, params, masks, bn_mean, bn_alpha, D):
+    """What the one-kernel AR entries stage -> (dev, zc, pc, pstride, mk, mean, alpha, Mz, Mp, M, N)."""
     _check3(z)
     dev = _lib.require_device()
-    zc = _stage(z.detach(), dev)
-    pc, pstride = _rows(params.detach(), dev)
-    mk = masks if (masks.device == dev and masks.dtype == torch.float32) else _stage(masks.float(), dev)
-    mean, alpha = _stats(bn_mean.reshape(-1), dev), _stats(bn_alpha.reshape(-1), dev)
-    Mz, N = zc.shape[0], zc.shape[1]
-    Mp = pc.shape[0]
-    M = _bcast_M(Mz, Mp)
-    if zc.shape[2] != D:
-        raise ValueError("last dimension of z (%d) must equal D (%d)" % (zc.shape[2], D))
-    nbytes = check(lib.tnf_ar_flow_workspace_bytes(Mp, D))
-    return dev, zc, pc, pstride, mk, mean, alpha, Mz, Mp, M, N, _workspace(nbytes, dev), nbytes
+    zc, pc, pstride, Mz, Mp, M, N = _pair(z.detach(), params.detach(), dev, D)
+    return (dev, zc, pc, pstride, _masks(masks, torch.float32, dev), _stats(bn_mean.reshape(-1), dev),
+            _stats(bn_alpha.reshape(-1), dev), Mz, Mp, M, N)
 
 
 def ar_flow_log_prob_raw(z, params, masks, bn_mean, bn_alpha, D, L, U, want_lp=True, want_z0=False, want_sld=False,
                          interval_consts=None):
     """tnf_ar_flow_log_prob_f32 -> (log_prob | None, z0 | None, sum_log_det | None) on z's device.
     interval_consts: the (7, D) device constants of a ToInterval support layer fused into the kernel."""
-    home = z.device
-    dev, zc, pc, pstride, mk, mean, alpha, Mz, Mp, M, N, ws, nbytes = _ar_common(z, params, masks, bn_mean, bn_alpha, D)
-    lp = torch.empty((M, N), dtype=torch.float32, device=dev) if want_lp else None
-    z0 = torch.empty((M, N, D), dtype=torch.float32, device=dev) if want_z0 else None
-    sld = torch.empty((M, N), dtype=torch.float32, device=dev) if want_sld else None
+    dev, zc, pc, pstride, mk, mean, alpha, Mz, Mp, M, N = _ar_prep(z, params, masks, bn_mean, bn_alpha, D)
+    lp, z0, sld = _empty_f32(want_lp, (M, N), dev), _empty_f32(want_z0, (M, N, D), dev), _empty_f32(want_sld, (M, N), dev)
+    ws, ws_bytes = _ws(check(lib.tnf_ar_flow_workspace_bytes(Mp, D)), dev)
     check(lib.tnf_ar_flow_log_prob_f32(zc.data_ptr(), pc.data_ptr(), mk.data_ptr(), mean.data_ptr(), alpha.data_ptr(),
-                                       None if interval_consts is None else interval_consts.data_ptr(),
-                                       lp.data_ptr() if want_lp else None, z0.data_ptr() if want_z0 else None,
-                                       sld.data_ptr() if want_sld else None, Mz, Mp, N, D, L, U, pstride,
-                                       ws.data_ptr(), nbytes, _lib.stream_ptr()))
-    if home != dev:
-        lp, z0, sld = (t if t is None else t.to(home) for t in (lp, z0, sld))
-    return lp, z0, sld
+                                       _ptr(interval_consts), _ptr(lp), _ptr(z0), _ptr(sld), Mz, Mp, N, D, L, U, pstride,
+                                       ws, ws_bytes, _lib.stream_ptr()))
+    return _home((lp, z0, sld), z.device, dev)
 
 
 def ar_flow_train_supported(M, Mp, D, L, U):
@@ -1494,8 +1264,7 @@ class _ArFlowLogProbFn(torch.autograd.Function):
         lp, _, _ = ar_flow_log_prob_raw(z, params, masks, bn_mean, bn_alpha, D, L, U, interval_consts=interval_consts)
         dev = _lib.require_device()
         pc, pstride = _rows(params.detach(), dev)
-        ctx.save_for_backward(_stage(z.detach(), dev), pc,
-                              masks if (masks.device == dev and masks.dtype == torch.float32) else _stage(masks.float(), dev),
+        ctx.save_for_backward(_stage(z.detach(), dev), pc, _masks(masks, torch.float32, dev),
                               _stats(bn_mean.reshape(-1), dev), _stats(bn_alpha.reshape(-1), dev))
         ctx.consts = interval_consts
         ctx.cfg = (D, L, U, pstride, params.device, tuple(params.shape))
@@ -1511,15 +1280,13 @@ class _ArFlowLogProbFn(torch.autograd.Function):
         Mp = pc.shape[0]
         g = _stage(g_lp.float(), dev)
         gp = torch.zeros(p_shape, dtype=torch.float32, device=dev)
-        nbytes = check(lib.tnf_ar_flow_bwd_workspace_bytes(Mp, D))
-        ws = _workspace(nbytes, dev)
+        ws, ws_bytes = _ws(check(lib.tnf_ar_flow_bwd_workspace_bytes(Mp, D)), dev)
         with operand_precision(ctx.prec):
             check(lib.tnf_ar_flow_log_prob_bwd_f32(zc.data_ptr(), pc.data_ptr(), mk.data_ptr(), mean.data_ptr(),
-                                                   alpha.data_ptr(),
-                                                   None if ctx.consts is None else ctx.consts.data_ptr(), g.data_ptr(),
-                                                   gp.data_ptr(), M, Mp, N, D, L, U, pstride, gp.shape[1], ws.data_ptr(),
-                                                   nbytes, _lib.stream_ptr()))
-        return None, (gp if p_home == dev else gp.to(p_home)), None, None, None, None, None, None, None
+                                                   alpha.data_ptr(), _ptr(ctx.consts), g.data_ptr(), gp.data_ptr(),
+                                                   M, Mp, N, D, L, U, pstride, gp.shape[1], ws, ws_bytes,
+                                                   _lib.stream_ptr()))
+        return None, _home(gp, p_home, dev), None, None, None, None, None, None, None
 
 
 def ar_flow_log_prob_train(z, params, masks, bn_mean, bn_alpha, interval_consts, D, L, U):
@@ -1528,12 +1295,11 @@ def ar_flow_log_prob_train(z, params, masks, bn_mean, bn_alpha, interval_consts,
 
 def ar_flow_forward_raw(omega, params, masks, bn_mean, bn_alpha, D, L, U, interval_consts=None):
     """tnf_ar_flow_forward_f32 (cached BatchNorm statistics) -> (z, sum_log_det) on the compute device."""
-    dev, zc, pc, pstride, mk, mean, alpha, Mz, Mp, M, N, ws, nbytes = _ar_common(omega, params, masks, bn_mean,
-                                                                               bn_alpha, D)
+    dev, oc, pc, pstride, mk, mean, alpha, Mz, Mp, M, N = _ar_prep(omega, params, masks, bn_mean, bn_alpha, D)
     z = torch.empty((M, N, D), dtype=torch.float32, device=dev)
     sld = torch.empty((M, N), dtype=torch.float32, device=dev)
-    check(lib.tnf_ar_flow_forward_f32(zc.data_ptr(), pc.data_ptr(), mk.data_ptr(), mean.data_ptr(), alpha.data_ptr(),
-                                      None if interval_consts is None else interval_consts.data_ptr(),
-                                      z.data_ptr(), sld.data_ptr(), Mz, Mp, N, D, L, U, pstride, ws.data_ptr(), nbytes,
-                                      _lib.stream_ptr()))
-    return z, sld
+    ws, ws_bytes = _ws(check(lib.tnf_ar_flow_workspace_bytes(Mp, D)), dev)
+    check(lib.tnf_ar_flow_forward_f32(oc.data_ptr(), pc.data_ptr(), mk.data_ptr(), mean.data_ptr(), alpha.data_ptr(),
+                                      _ptr(interval_consts), z.data_ptr(), sld.data_ptr(), Mz, Mp, N, D, L, U, pstride,
+                                      ws, ws_bytes, _lib.stream_ptr()))
+    return z, sld  # on the compute device: the caller carries on there
