@@ -1,9 +1,8 @@
 // C-ABI entry points of libtnf_hip.so (declared in include/tnf.h): argument checks,
 // kernel selection and the launch sequences of the flow-level chains.
-#include <string.h>
-
 #include <atomic>
 
+#include "flow_layer.h"
 #include "tnf_common.h"
 
 namespace tnf {
@@ -51,19 +50,58 @@ static int check_mnd(const char* fn, int64_t Mz, int64_t Mp, int64_t N, int D) {
     return TNF_OK;
 }
 
+// ---- argument checks the entries share; `fn` is the entry's name, which every message starts with ----
+static int check_dtype(const char* fn, int dtype) {
+    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "%s: dtype %d", fn, dtype);
+    return TNF_OK;
+}
+
+// the training entries' batch: M contexts of N samples, one parameter row or one per context
+static inline bool bad_batch(int64_t M, int64_t M_p, int64_t N) { return M < 1 || (M_p != 1 && M_p != M) || N < 0; }
+static int check_batch(const char* fn, int64_t M, int64_t M_p, int64_t N) {
+    if (bad_batch(M, M_p, N)) return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld", fn, (long long)M, (long long)M_p, (long long)N);
+    return TNF_OK;
+}
+static int check_batch_stages(const char* fn, int64_t M, int64_t M_p, int64_t N, int S) {
+    if (bad_batch(M, M_p, N) || S < 1)
+        return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld S=%d", fn, (long long)M, (long long)M_p, (long long)N, S);
+    return TNF_OK;
+}
+
+static int check_flow_row(const char* fn, int64_t pstride, int D, int S, int L, int U) {
+    const int64_t need = flow_layout(D, S, L, U).total;
+    if (pstride < need)
+        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride, (long long)need);
+    return TNF_OK;
+}
+
+static int check_workspace(const char* fn, const void* ws, int64_t ws_bytes, int64_t need) {
+    if (!ws || ws_bytes < need) return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes, (long long)need);
+    return TNF_OK;
+}
+
+// the conditional-flow entries: batch, shape and the leading dimensions of h and W
+static int check_cond_flow(const char* fn, int64_t M, int D, int S, int L, int U, int H, int64_t ldh, int64_t ldw) {
+    if (M < 0) return fail(TNF_EINVAL, "%s: M=%lld", fn, (long long)M);
+    if (!cond_flow_supported(D, S, L, U, H))
+        return fail(TNF_EUNSUPPORTED, "%s: no kernel for D=%d S=%d L=%d U=%d H=%d", fn, D, S, L, U, H);
+    if (ldh < H || ldw < H || (ldh & 3) || (ldw & 3))
+        return fail(TNF_EINVAL, "%s: ldh=%lld ldw=%lld must be multiples of 4 and >= H=%d", fn, (long long)ldh, (long long)ldw, H);
+    return TNF_OK;
+}
+
 static int64_t round16(int64_t b) { return (b + 15) & ~(int64_t)15; }
+static inline float* ws_floats(void* ws, int64_t byte_offset) {  // a region of a caller's workspace
+    return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + byte_offset);
+}
 
 struct FlowWs {
     int64_t fold, ldc, images, zbuf, ldbuf, total;
 };
 static int64_t flow_image_slot(int D, int L, int U) {
-    // narrow shapes: fp32 and split-f16 images share one slot size (the L = 3 fp32 image);
-    // wide shapes: the wide image of exactly this (D, L, U)
-    if (!mfma_supported(D, L, U)) return wide_image_floats(D, L, U);
     // narrow shapes: fp32 and split-f16 images share one slot size (the L = 3 fp32 image); flow_ws takes the larger of
-    // this and flow_prep_slot (the layer-range chain's prepared prologues)
-    const int64_t a = mfma_image_floats(D, 3);
-    return a;
+    // this and flow_prep_slot (the layer-range chain's prepared prologues).  Wide shapes: the image of exactly (D, L, U)
+    return mfma_supported(D, L, U) ? mfma_image_floats(D, 3) : wide_image_floats(D, L, U);
 }
 static int64_t flow_prep_slot(int D, int S, int L, int U) {
     // per layer, so that 2S slots hold a chain's prepared prologues -- for EVERY number of layers per launch the chain
@@ -82,7 +120,8 @@ static FlowWs flow_ws(int64_t M, int64_t N, int D, int S, int L, int U) {
     w.fold = 0;
     w.ldc = round16(M * 2 * S * 2 * D * (int64_t)sizeof(float));
     w.images = w.ldc + round16(M * (int64_t)sizeof(float));
-    const int64_t slot = flow_image_slot(D, L, U) > flow_prep_slot(D, S, L, U) ? flow_image_slot(D, L, U) : flow_prep_slot(D, S, L, U);
+    const int64_t image = flow_image_slot(D, L, U), prep = flow_prep_slot(D, S, L, U);
+    const int64_t slot = image > prep ? image : prep;
     w.zbuf = w.images + round16(M * 2 * S * slot * (int64_t)sizeof(float));
     w.ldbuf = w.zbuf + round16(M * N * D * (int64_t)sizeof(float));
     w.total = w.ldbuf + round16(M * N * (int64_t)sizeof(float));
@@ -120,38 +159,29 @@ int tnf_gated_copy_f32(const int32_t* flag, float* dst, const float* src, int64_
     return check_launch("gated_copy");
 }
 
+// the calling thread's variable behind an option key, or NULL
+static int* option_var(int32_t key) {
+    switch (key) {
+        case TNF_OPT_FORCE_GENERIC: return &g_force_generic;
+        case TNF_OPT_FLOW_VARIANT: return &g_flow_variant;
+        case TNF_OPT_LAYER_VARIANT: return &g_layer_variant;
+        case TNF_OPT_COND_VARIANT: return &g_cond_variant;
+        case TNF_OPT_TRAIN_BWD_FP32: return &g_train_bwd_fp32;
+        case TNF_OPT_OPERAND_PREC: return &g_operand_prec;
+        case TNF_OPT_REV_VARIANT: return &g_rev_variant;
+    }
+    return nullptr;
+}
+
 int tnf_set_option(int32_t key, int32_t value) {
-    if (key == TNF_OPT_FORCE_GENERIC) {
-        g_force_generic = value;
-        return TNF_OK;
-    }
-    if (key == TNF_OPT_OPERAND_PREC) {
-        if (value != 0 && value != 1) return fail(TNF_EINVAL, "tnf_set_option: operand precision %d", value);
-        g_operand_prec = value;
-        return TNF_OK;
-    }
-    if (key == TNF_OPT_FLOW_VARIANT) {
-        g_flow_variant = value;
-        return TNF_OK;
-    }
-    if (key == TNF_OPT_TRAIN_BWD_FP32) {
-        g_train_bwd_fp32 = value;
-        return TNF_OK;
-    }
-    if (key == TNF_OPT_LAYER_VARIANT) {
-        g_layer_variant = value;
-        return TNF_OK;
-    }
-    if (key == TNF_OPT_COND_VARIANT) {
-        g_cond_variant = value;
-        return TNF_OK;
-    }
-    if (key == TNF_OPT_REV_VARIANT) {
-        if (value != 0 && value != 1) return fail(TNF_EINVAL, "tnf_set_option: reversible-backward variant %d", value);
-        g_rev_variant = value;
-        return TNF_OK;
-    }
-    return fail(TNF_EINVAL, "tnf_set_option: unknown key %d", key);
+    int* var = option_var(key);
+    if (!var) return fail(TNF_EINVAL, "tnf_set_option: unknown key %d", key);
+    if (key == TNF_OPT_OPERAND_PREC && value != 0 && value != 1)
+        return fail(TNF_EINVAL, "tnf_set_option: operand precision %d", value);
+    if (key == TNF_OPT_REV_VARIANT && value != 0 && value != 1)
+        return fail(TNF_EINVAL, "tnf_set_option: reversible-backward variant %d", value);
+    *var = value;
+    return TNF_OK;
 }
 
 int64_t tnf_diag_launch_count(int32_t family) {
@@ -161,16 +191,10 @@ int64_t tnf_diag_launch_count(int32_t family) {
 
 int tnf_get_option(int32_t key, int32_t* value) {
     if (!value) return fail(TNF_EINVAL, "tnf_get_option: value is NULL");
-    switch (key) {
-        case TNF_OPT_FORCE_GENERIC: *value = g_force_generic; return TNF_OK;
-        case TNF_OPT_FLOW_VARIANT: *value = g_flow_variant; return TNF_OK;
-        case TNF_OPT_LAYER_VARIANT: *value = g_layer_variant; return TNF_OK;
-        case TNF_OPT_COND_VARIANT: *value = g_cond_variant; return TNF_OK;
-        case TNF_OPT_TRAIN_BWD_FP32: *value = g_train_bwd_fp32; return TNF_OK;
-        case TNF_OPT_OPERAND_PREC: *value = g_operand_prec; return TNF_OK;
-        case TNF_OPT_REV_VARIANT: *value = g_rev_variant; return TNF_OK;
-    }
-    return fail(TNF_EINVAL, "tnf_get_option: unknown key %d", key);
+    const int* var = option_var(key);
+    if (!var) return fail(TNF_EINVAL, "tnf_get_option: unknown key %d", key);
+    *value = *var;
+    return TNF_OK;
 }
 
 int64_t tnf_coupling_num_params(int32_t D, int32_t L, int32_t U, int32_t upper) {
@@ -191,7 +215,7 @@ int tnf_has_fast_path(int32_t D, int32_t L, int32_t U) {
 int tnf_coupling(int32_t dtype, const void* z, const void* params, void* z_out, void* log_det,
                  int64_t M_z, int64_t M_p, int64_t N, int32_t D, int32_t L, int32_t U,
                  int32_t upper, int32_t inverse, int64_t pstride, int32_t ld_mode, void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_coupling: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_coupling", dtype)) return rc;
     int rc = check_mnd("tnf_coupling", M_z, M_p, N, D);
     if (rc) return rc;
     if (D < 2) return fail(TNF_EINVAL, "tnf_coupling: D=%d needs both halves non-empty", D);
@@ -206,10 +230,10 @@ int tnf_coupling(int32_t dtype, const void* z, const void* params, void* z_out, 
     if (N == 0) return TNF_OK;
     hipStream_t st = as_stream(stream);
     const int64_t Mmax = M_z > M_p ? M_z : M_p;
-    if (dtype == TNF_F32 && !g_force_generic && mfma_supported(D, L, U) && (N >= 16 || Mmax >= 8) &&
-        aligned16(z) && aligned16(z_out)) {
-        MfmaLayerArgs a;
-        memset(&a, 0, sizeof(a));
+    const bool fast = dtype == TNF_F32 && !g_force_generic && aligned16(z) && aligned16(z_out);
+    const bool narrow = fast && mfma_supported(D, L, U) && (N >= 16 || Mmax >= 8);
+    if (narrow || (fast && wide_supported(D, L, U) && N >= 16)) {
+        MfmaLayerArgs a = {};
         a.z = (const float*)z;
         a.z_out = (float*)z_out;
         a.params = (const float*)params;
@@ -219,21 +243,7 @@ int tnf_coupling(int32_t dtype, const void* z, const void* params, void* z_out, 
         a.ld_sign = ld_mode == TNF_LD_SUB ? -1.f : 1.f;
         a.Mz = M_z; a.Mp = M_p; a.N = N;
         a.D = D; a.L = L; a.U = U; a.upper = upper; a.inverse = inverse;
-        return launch_coupling_mfma(a, st);
-    }
-    if (dtype == TNF_F32 && !g_force_generic && wide_supported(D, L, U) && N >= 16 && aligned16(z) && aligned16(z_out)) {
-        MfmaLayerArgs a;
-        memset(&a, 0, sizeof(a));
-        a.z = (const float*)z;
-        a.z_out = (float*)z_out;
-        a.params = (const float*)params;
-        a.pstride = pstride;
-        a.ld_in = ld_mode == TNF_LD_STORE ? nullptr : (const float*)log_det;
-        a.ld_out = (float*)log_det;
-        a.ld_sign = ld_mode == TNF_LD_SUB ? -1.f : 1.f;
-        a.Mz = M_z; a.Mp = M_p; a.N = N;
-        a.D = D; a.L = L; a.U = U; a.upper = upper; a.inverse = inverse;
-        return launch_coupling_wide(a, st);
+        return narrow ? launch_coupling_mfma(a, st) : launch_coupling_wide(a, st);
     }
     return launch_coupling_generic(dtype, z, params, z_out, log_det, M_z, M_p, N, D, L, U, upper,
                                    inverse, pstride, ld_mode, st);
@@ -242,7 +252,7 @@ int tnf_coupling(int32_t dtype, const void* z, const void* params, void* z_out, 
 int tnf_affine(int32_t dtype, const void* z, const void* params, void* z_out, void* log_det,
                int64_t M_z, int64_t M_p, int64_t N, int32_t D, int32_t inverse, int64_t pstride,
                void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_affine: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_affine", dtype)) return rc;
     int rc = check_mnd("tnf_affine", M_z, M_p, N, D);
     if (rc) return rc;
     if (pstride < 2 * (int64_t)D)
@@ -254,7 +264,7 @@ int tnf_affine(int32_t dtype, const void* z, const void* params, void* z_out, vo
 
 int tnf_bn_apply(int32_t dtype, const void* z, const float* mean, const float* alpha, void* z_out,
                  float* log_det, int64_t rows, int32_t D, int32_t inverse, void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_bn_apply: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_bn_apply", dtype)) return rc;
     if (rows < 0 || D < 1) return fail(TNF_EINVAL, "tnf_bn_apply: rows=%lld D=%d", (long long)rows, D);
     if (!z || !mean || !alpha || !z_out || !log_det) return fail(TNF_EINVAL, "tnf_bn_apply: NULL pointer");
     return launch_bn_apply(dtype, z, mean, alpha, z_out, log_det, rows, D, inverse, as_stream(stream));
@@ -272,9 +282,7 @@ int tnf_bn_batch_forward_f32(const float* z, float* z_out, float* mean_out, floa
         return fail(TNF_EINVAL, "tnf_bn_batch_forward_f32: rows=%lld (need > 1 value per feature) D=%d", (long long)rows, D);
     if (!z || !z_out || !mean_out || !alpha_out || !log_det || !workspace)
         return fail(TNF_EINVAL, "tnf_bn_batch_forward_f32: NULL pointer");
-    if (workspace_bytes < tnf_bn_batch_workspace_bytes(D))
-        return fail(TNF_EWORKSPACE, "tnf_bn_batch_forward_f32: workspace %lld < %lld", (long long)workspace_bytes,
-                    (long long)tnf_bn_batch_workspace_bytes(D));
+    if (int rc = check_workspace("tnf_bn_batch_forward_f32", workspace, workspace_bytes, tnf_bn_batch_workspace_bytes(D))) return rc;
     return launch_bn_batch_forward(z, z_out, mean_out, alpha_out, log_det, rows, D, eps, workspace,
                                    as_stream(stream));
 }
@@ -283,8 +291,8 @@ static int coupling_backward_impl(int32_t dtype, const void* z, const void* para
                           const void* g_log_det, void* g_z, void* g_params, int64_t M, int64_t M_p,
                           int64_t N, int32_t D, int32_t L, int32_t U, int32_t upper, int32_t inverse,
                           int64_t pstride, int64_t gpstride, void* stream, void* ws, int64_t ws_bytes) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_coupling_backward: dtype %d", dtype);
-    if (M < 1 || N < 0 || D < 2 || L < 1 || U < 1 || (M_p != 1 && M_p != M))
+    if (int rc = check_dtype("tnf_coupling_backward", dtype)) return rc;
+    if (bad_batch(M, M_p, N) || D < 2 || L < 1 || U < 1)
         return fail(TNF_EINVAL, "tnf_coupling_backward: M=%lld M_p=%lld N=%lld D=%d L=%d U=%d", (long long)M,
                     (long long)M_p, (long long)N, D, L, U);
     const int64_t need = coupling_num_params(D, L, U, upper);
@@ -322,7 +330,7 @@ int tnf_coupling_backward(int32_t dtype, const void* z, const void* params, cons
 
 int64_t tnf_coupling_backward_workspace_bytes(int32_t dtype, int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t L,
                                               int32_t U, int32_t upper) {
-    if ((dtype != TNF_F32 && dtype != TNF_F64) || M < 1 || N < 0 || D < 2 || L < 1 || U < 1 || (M_p != 1 && M_p != M))
+    if ((dtype != TNF_F32 && dtype != TNF_F64) || bad_batch(M, M_p, N) || D < 2 || L < 1 || U < 1)
         return fail(TNF_EINVAL, "tnf_coupling_backward_workspace_bytes: dtype=%d M=%lld M_p=%lld N=%lld D=%d L=%d U=%d", dtype,
                     (long long)M, (long long)M_p, (long long)N, D, L, U);
     if (dtype == TNF_F32 && !g_force_generic && mfma_supported(D, L, U) && N >= 16) return 0;  // the MFMA kernel takes none
@@ -348,8 +356,8 @@ int tnf_affine_backward(int32_t dtype, const void* z, const void* params, const 
                         const void* g_log_det, void* g_z, void* g_params, int64_t M, int64_t M_p,
                         int64_t N, int32_t D, int32_t inverse, int64_t pstride, int64_t gpstride,
                         void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_affine_backward: dtype %d", dtype);
-    if (M < 1 || N < 0 || D < 1 || (M_p != 1 && M_p != M))
+    if (int rc = check_dtype("tnf_affine_backward", dtype)) return rc;
+    if (bad_batch(M, M_p, N) || D < 1)
         return fail(TNF_EINVAL, "tnf_affine_backward: M=%lld M_p=%lld N=%lld D=%d", (long long)M, (long long)M_p,
                     (long long)N, D);
     if (pstride < 2 * (int64_t)D || gpstride < 2 * (int64_t)D)
@@ -362,7 +370,7 @@ int tnf_affine_backward(int32_t dtype, const void* z, const void* params, const 
 
 int tnf_bn_apply_backward(int32_t dtype, const void* g_z_out, const float* alpha, void* g_z, int64_t rows,
                           int32_t D, int32_t inverse, void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_bn_apply_backward: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_bn_apply_backward", dtype)) return rc;
     if (rows < 0 || D < 1) return fail(TNF_EINVAL, "tnf_bn_apply_backward: rows=%lld D=%d", (long long)rows, D);
     if (!alpha || (rows > 0 && (!g_z_out || !g_z))) return fail(TNF_EINVAL, "tnf_bn_apply_backward: NULL pointer");
     return launch_bn_apply_backward(dtype, g_z_out, alpha, g_z, rows, D, inverse, as_stream(stream));
@@ -374,9 +382,7 @@ int tnf_bn_batch_backward_f32(const float* z_norm, const float* g_z_out, const f
     if (rows < 2 || D < 1) return fail(TNF_EINVAL, "tnf_bn_batch_backward_f32: rows=%lld D=%d", (long long)rows, D);
     if (!z_norm || !g_z_out || !alpha || !g_z || !workspace)
         return fail(TNF_EINVAL, "tnf_bn_batch_backward_f32: NULL pointer");
-    if (workspace_bytes < tnf_bn_batch_workspace_bytes(D))
-        return fail(TNF_EWORKSPACE, "tnf_bn_batch_backward_f32: workspace %lld < %lld", (long long)workspace_bytes,
-                    (long long)tnf_bn_batch_workspace_bytes(D));
+    if (int rc = check_workspace("tnf_bn_batch_backward_f32", workspace, workspace_bytes, tnf_bn_batch_workspace_bytes(D))) return rc;
     return launch_bn_batch_backward(z_norm, g_z_out, g_log_det, alpha, g_z, rows, D, workspace, as_stream(stream));
 }
 
@@ -392,9 +398,7 @@ int tnf_bn_batch_normalize_f32(const float* z, const double* moments, float* z_o
     if (rows < 0 || D < 1) return fail(TNF_EINVAL, "tnf_bn_batch_normalize_f32: rows=%lld D=%d", (long long)rows, D);
     if (!moments || !mean_out || !alpha_out || !log_det || !workspace || (rows > 0 && (!z || !z_out)))
         return fail(TNF_EINVAL, "tnf_bn_batch_normalize_f32: NULL pointer");
-    if (workspace_bytes < (int64_t)D * (int64_t)sizeof(float))
-        return fail(TNF_EWORKSPACE, "tnf_bn_batch_normalize_f32: workspace %lld < %lld", (long long)workspace_bytes,
-                    (long long)D * (long long)sizeof(float));
+    if (int rc = check_workspace("tnf_bn_batch_normalize_f32", workspace, workspace_bytes, (int64_t)D * (int64_t)sizeof(float))) return rc;
     return launch_bn_normalize_from_moments(z, moments, z_out, mean_out, alpha_out, log_det,
                                             reinterpret_cast<float*>(workspace), rows, D, eps, as_stream(stream));
 }
@@ -422,7 +426,7 @@ int64_t tnf_maf_num_params(int32_t D, int32_t L, int32_t U) {
 int tnf_maf(int32_t dtype, const void* z, const void* params, const void* masks, void* z_out, void* log_det,
             int64_t M_z, int64_t M_p, int64_t N, int32_t D, int32_t L, int32_t U, int32_t inverse, int64_t pstride,
             void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_maf: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_maf", dtype)) return rc;
     int rc = check_mnd("tnf_maf", M_z, M_p, N, D);
     if (rc) return rc;
     if (L < 1 || U < 1) return fail(TNF_EINVAL, "tnf_maf: num_layers=%d num_units=%d", L, U);
@@ -461,9 +465,8 @@ static int ar_flow_run(const char* fn, int inverse, const float* z, const float*
         return fail(TNF_EINVAL, "%s: params row has %lld elements, the flow needs %lld", fn, (long long)pstride,
                     (long long)(p_maf + 2 * D));
     if (!z || !params || !masks || !bn_mean || !bn_alpha || !workspace) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (workspace_bytes < tnf_ar_flow_workspace_bytes(M_p, D))
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)workspace_bytes,
-                    (long long)tnf_ar_flow_workspace_bytes(M_p, D));
+    rc = check_workspace(fn, workspace, workspace_bytes, tnf_ar_flow_workspace_bytes(M_p, D));
+    if (rc) return rc;
     if (N == 0) return TNF_OK;
     float* fold = (float*)workspace;
     float* ldc = fold + M_p * 2 * (int64_t)D;
@@ -518,23 +521,22 @@ int tnf_ar_flow_log_prob_bwd_f32(const float* z, const float* params, const floa
                                  int64_t pstride, int64_t gpstride, void* workspace, int64_t workspace_bytes,
                                  void* stream) {
     const char* fn = "tnf_ar_flow_log_prob_bwd_f32";
-    if (M < 1 || N < 0 || (M_p != 1 && M_p != M))
-        return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld", fn, (long long)M, (long long)M_p, (long long)N);
+    int rc = check_batch(fn, M, M_p, N);
+    if (rc) return rc;
     if (!tnf_ar_flow_train_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "%s: no kernel for D=%d L=%d U=%d", fn, D, L, U);
     const int64_t p_maf = tnf_maf_num_params(D, L, U);
     if (pstride < p_maf + 2 * (int64_t)D || gpstride < p_maf + 2 * (int64_t)D)
         return fail(TNF_EINVAL, "%s: parameter rows shorter than %lld", fn, (long long)(p_maf + 2 * D));
     if (!z || !params || !masks || !bn_mean || !bn_alpha || !g_log_prob || !g_params || !workspace)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (workspace_bytes < tnf_ar_flow_bwd_workspace_bytes(M_p, D))
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)workspace_bytes,
-                    (long long)tnf_ar_flow_bwd_workspace_bytes(M_p, D));
+    rc = check_workspace(fn, workspace, workspace_bytes, tnf_ar_flow_bwd_workspace_bytes(M_p, D));
+    if (rc) return rc;
     if (N == 0) return TNF_OK;
     float* fold = (float*)workspace;
     float* ldc = fold + M_p * 2 * (int64_t)D;
     float* g_fold = ldc + M_p;
     float* glp_sum = g_fold + M_p * 2 * (int64_t)D;
-    int rc = launch_ar_fold(params, pstride, p_maf, bn_mean, bn_alpha, fold, ldc, M_p, D, 1, as_stream(stream));
+    rc = launch_ar_fold(params, pstride, p_maf, bn_mean, bn_alpha, fold, ldc, M_p, D, 1, as_stream(stream));
     if (rc) return rc;
     return launch_ar_flow_backward(z, params, masks, fold, interval_consts, g_log_prob, g_params, g_fold, glp_sum, M, M_p,
                                    N, D, L, U, pstride, gpstride, as_stream(stream));
@@ -546,7 +548,7 @@ int tnf_ar_flow_log_prob_bwd_f32(const float* z, const float* params, const floa
 int tnf_maf_inverse_alpha(int32_t dtype, const void* z, const void* params, const void* masks, void* z_out, void* log_det,
                           void* alpha_out, int64_t M_z, int64_t M_p, int64_t N, int32_t D, int32_t L, int32_t U,
                           int64_t pstride, void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_maf_inverse_alpha: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_maf_inverse_alpha", dtype)) return rc;
     int rc = check_mnd("tnf_maf_inverse_alpha", M_z, M_p, N, D);
     if (rc) return rc;
     if (L < 1 || U < 1) return fail(TNF_EINVAL, "tnf_maf_inverse_alpha: L=%d U=%d", L, U);
@@ -561,8 +563,8 @@ int tnf_maf_inverse_alpha(int32_t dtype, const void* z, const void* params, cons
 static int maf_backward_impl(int32_t dtype, const void* z, const void* params, const void* masks, const void* g_z_out,
                      const void* g_log_det, void* g_z, void* g_params, int64_t M, int64_t M_p, int64_t N, int32_t D,
                      int32_t L, int32_t U, int64_t pstride, int64_t gpstride, void* stream, void* ws, int64_t ws_bytes) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_maf_backward: dtype %d", dtype);
-    if (M < 1 || N < 0 || D < 1 || L < 1 || U < 1 || (M_p != 1 && M_p != M))
+    if (int rc = check_dtype("tnf_maf_backward", dtype)) return rc;
+    if (bad_batch(M, M_p, N) || D < 1 || L < 1 || U < 1)
         return fail(TNF_EINVAL, "tnf_maf_backward: M=%lld M_p=%lld N=%lld D=%d L=%d U=%d", (long long)M,
                     (long long)M_p, (long long)N, D, L, U);
     const int64_t need = tnf_maf_num_params(D, L, U);
@@ -593,7 +595,7 @@ int tnf_maf_backward(int32_t dtype, const void* z, const void* params, const voi
 }
 
 int64_t tnf_maf_backward_workspace_bytes(int32_t dtype, int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t L, int32_t U) {
-    if ((dtype != TNF_F32 && dtype != TNF_F64) || M < 1 || N < 0 || D < 1 || L < 1 || U < 1 || (M_p != 1 && M_p != M))
+    if ((dtype != TNF_F32 && dtype != TNF_F64) || bad_batch(M, M_p, N) || D < 1 || L < 1 || U < 1)
         return fail(TNF_EINVAL, "tnf_maf_backward_workspace_bytes: dtype=%d M=%lld M_p=%lld N=%lld D=%d L=%d U=%d", dtype,
                     (long long)M, (long long)M_p, (long long)N, D, L, U);
     if (dtype == TNF_F32 && !g_force_generic && maf_bwd_mfma_supported(D, L, U)) return 0;  // the MFMA kernel takes none
@@ -629,21 +631,16 @@ int tnf_cond_flow_log_prob_f32(const float* z, const float* h, const float* W, c
                                const float* bn_mean, const float* bn_alpha, float* log_prob, float* z0,
                                float* sum_log_det, int64_t M, int32_t D, int32_t S, int32_t L, int32_t U, int32_t H,
                                int64_t ldh, int64_t ldw, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (M < 0) return fail(TNF_EINVAL, "tnf_cond_flow_log_prob_f32: M=%lld", (long long)M);
-    if (!cond_flow_supported(D, S, L, U, H))
-        return fail(TNF_EUNSUPPORTED, "tnf_cond_flow_log_prob_f32: no kernel for D=%d S=%d L=%d U=%d H=%d", D, S, L, U, H);
-    if (ldh < H || ldw < H || (ldh & 3) || (ldw & 3))
-        return fail(TNF_EINVAL, "tnf_cond_flow_log_prob_f32: ldh=%lld ldw=%lld must be multiples of 4 and >= H=%d",
-                    (long long)ldh, (long long)ldw, H);
+    const char* fn = "tnf_cond_flow_log_prob_f32";
+    int rc = check_cond_flow(fn, M, D, S, L, U, H, ldh, ldw);
+    if (rc) return rc;
     if (M == 0) return TNF_OK;
     if (!z || !h || !W || !b || !bn_mean || !bn_alpha || !log_prob || !workspace)
-        return fail(TNF_EINVAL, "tnf_cond_flow_log_prob_f32: NULL pointer");
+        return fail(TNF_EINVAL, "%s: NULL pointer", fn);
     if (((uintptr_t)h & 15) || ((uintptr_t)W & 15) || ((uintptr_t)z & 15) || ((uintptr_t)workspace & 255))
-        return fail(TNF_EINVAL, "tnf_cond_flow_log_prob_f32: z, h, W must be 16-byte and the workspace 256-byte aligned");
-    const int64_t need = cond_flow_workspace(D, S, L, U, H);
-    if (workspace_bytes < need)
-        return fail(TNF_EWORKSPACE, "tnf_cond_flow_log_prob_f32: workspace %lld < %lld", (long long)workspace_bytes,
-                    (long long)need);
+        return fail(TNF_EINVAL, "%s: z, h, W must be 16-byte and the workspace 256-byte aligned", fn);
+    rc = check_workspace(fn, workspace, workspace_bytes, cond_flow_workspace(D, S, L, U, H));
+    if (rc) return rc;
     return launch_cond_flow_log_prob(z, h, W, b, bn_mean, bn_alpha, log_prob, z0, sum_log_det, nullptr, M, D, S, L, U,
                                      H, ldh, ldw, workspace, as_stream(stream));
 }
@@ -652,22 +649,17 @@ int tnf_cond_flow_forward_f32(const float* omega, const float* h, const float* W
                               const float* bn_mean, const float* bn_alpha, float* z_out, float* sum_log_det, int64_t M,
                               int32_t D, int32_t S, int32_t L, int32_t U, int32_t H, int64_t ldh, int64_t ldw,
                               void* workspace, int64_t workspace_bytes, void* stream) {
-    if (M < 0) return fail(TNF_EINVAL, "tnf_cond_flow_forward_f32: M=%lld", (long long)M);
-    if (!cond_flow_supported(D, S, L, U, H))
-        return fail(TNF_EUNSUPPORTED, "tnf_cond_flow_forward_f32: no kernel for D=%d S=%d L=%d U=%d H=%d", D, S, L, U, H);
-    if (ldh < H || ldw < H || (ldh & 3) || (ldw & 3))
-        return fail(TNF_EINVAL, "tnf_cond_flow_forward_f32: ldh=%lld ldw=%lld must be multiples of 4 and >= H=%d",
-                    (long long)ldh, (long long)ldw, H);
+    const char* fn = "tnf_cond_flow_forward_f32";
+    int rc = check_cond_flow(fn, M, D, S, L, U, H, ldh, ldw);
+    if (rc) return rc;
     if (M == 0) return TNF_OK;
     if (!omega || !h || !W || !b || !bn_mean || !bn_alpha || !z_out || !sum_log_det || !workspace)
-        return fail(TNF_EINVAL, "tnf_cond_flow_forward_f32: NULL pointer");
+        return fail(TNF_EINVAL, "%s: NULL pointer", fn);
     if (((uintptr_t)h & 15) || ((uintptr_t)W & 15) || ((uintptr_t)omega & 15) || ((uintptr_t)z_out & 15) ||
         ((uintptr_t)workspace & 255))
-        return fail(TNF_EINVAL, "tnf_cond_flow_forward_f32: omega, z_out, h, W must be 16-byte and the workspace 256-byte aligned");
-    const int64_t need = cond_flow_workspace(D, S, L, U, H);
-    if (workspace_bytes < need)
-        return fail(TNF_EWORKSPACE, "tnf_cond_flow_forward_f32: workspace %lld < %lld", (long long)workspace_bytes,
-                    (long long)need);
+        return fail(TNF_EINVAL, "%s: omega, z_out, h, W must be 16-byte and the workspace 256-byte aligned", fn);
+    rc = check_workspace(fn, workspace, workspace_bytes, cond_flow_workspace(D, S, L, U, H));
+    if (rc) return rc;
     return launch_cond_flow_forward(omega, h, W, b, bn_mean, bn_alpha, z_out, sum_log_det, M, D, S, L, U, H, ldh, ldw,
                                     workspace, as_stream(stream));
 }
@@ -689,13 +681,11 @@ int64_t tnf_cond_flow_bwd_workspace_bytes(int32_t D, int32_t S, int32_t L, int32
     return cond_flow_bwd_workspace(D, S, L, U, H);
 }
 
+// the training pair checks the alignment of h, W and the workspace before anything else that can end the call
 static int cond_train_checks(const char* fn, int64_t M, int D, int S, int L, int U, int H, int64_t ldh, int64_t ldw,
                              const void* h, const void* W, const void* ws) {
-    if (M < 0) return fail(TNF_EINVAL, "%s: M=%lld", fn, (long long)M);
-    if (!cond_flow_supported(D, S, L, U, H))
-        return fail(TNF_EUNSUPPORTED, "%s: no kernel for D=%d S=%d L=%d U=%d H=%d", fn, D, S, L, U, H);
-    if (ldh < H || ldw < H || (ldh & 3) || (ldw & 3))
-        return fail(TNF_EINVAL, "%s: ldh=%lld ldw=%lld must be multiples of 4 and >= H=%d", fn, (long long)ldh, (long long)ldw, H);
+    int rc = check_cond_flow(fn, M, D, S, L, U, H, ldh, ldw);
+    if (rc) return rc;
     if (((uintptr_t)h & 15) || ((uintptr_t)W & 15) || ((uintptr_t)ws & 255))
         return fail(TNF_EINVAL, "%s: h, W must be 16-byte and the workspace 256-byte aligned", fn);
     return TNF_OK;
@@ -712,9 +702,8 @@ int tnf_cond_flow_log_prob_fwd_f32(const float* z, const float* h, const float* 
         return fail(TNF_EINVAL, "tnf_cond_flow_log_prob_fwd_f32: NULL pointer");
     if (((uintptr_t)z & 15) || ((uintptr_t)acts & 15))
         return fail(TNF_EINVAL, "tnf_cond_flow_log_prob_fwd_f32: z and acts must be 16-byte aligned");
-    if (workspace_bytes < cond_flow_workspace(D, S, L, U, H))
-        return fail(TNF_EWORKSPACE, "tnf_cond_flow_log_prob_fwd_f32: workspace %lld < %lld", (long long)workspace_bytes,
-                    (long long)cond_flow_workspace(D, S, L, U, H));
+    rc = check_workspace("tnf_cond_flow_log_prob_fwd_f32", workspace, workspace_bytes, cond_flow_workspace(D, S, L, U, H));
+    if (rc) return rc;
     return launch_cond_flow_log_prob(z, h, W, b, bn_mean, bn_alpha, log_prob, nullptr, nullptr, acts, M, D, S, L, U, H,
                                      ldh, ldw, workspace, as_stream(stream));
 }
@@ -740,16 +729,15 @@ int tnf_cond_flow_log_prob_bwd_f32(const float* g_log_prob, const float* h, cons
         return fail(TNF_EINVAL, "tnf_cond_flow_log_prob_bwd_f32: NULL pointer");
     if (((uintptr_t)acts & 15) || ((uintptr_t)deltas & 15) || ((uintptr_t)g_h & 15) || ((uintptr_t)g_z & 15))
         return fail(TNF_EINVAL, "tnf_cond_flow_log_prob_bwd_f32: acts, deltas, g_h, g_z must be 16-byte aligned");
-    if (workspace_bytes < cond_flow_bwd_workspace(D, S, L, U, H))
-        return fail(TNF_EWORKSPACE, "tnf_cond_flow_log_prob_bwd_f32: workspace %lld < %lld", (long long)workspace_bytes,
-                    (long long)cond_flow_bwd_workspace(D, S, L, U, H));
+    rc = check_workspace("tnf_cond_flow_log_prob_bwd_f32", workspace, workspace_bytes, cond_flow_bwd_workspace(D, S, L, U, H));
+    if (rc) return rc;
     return launch_cond_flow_backward(g_log_prob, h, W, b, bn_mean, bn_alpha, acts, deltas, g_h, g_W, g_b, g_z, M, D, S, L,
                                      U, H, ldh, ldw, ldgh, ldgw, workspace, as_stream(stream));
 }
 
 int tnf_to_interval(int32_t dtype, const void* z, const float* consts, void* z_out, void* log_det, int64_t rows,
                     int32_t D, int32_t inverse, void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_to_interval: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_to_interval", dtype)) return rc;
     if (rows < 0 || D < 1) return fail(TNF_EINVAL, "tnf_to_interval: rows=%lld D=%d", (long long)rows, D);
     if (rows == 0) return TNF_OK;
     if (!z || !consts || !z_out || !log_det) return fail(TNF_EINVAL, "tnf_to_interval: NULL pointer");
@@ -759,7 +747,7 @@ int tnf_to_interval(int32_t dtype, const void* z, const float* consts, void* z_o
 int tnf_to_interval_backward(int32_t dtype, const void* z, const float* consts, const void* g_z_out,
                              const void* g_log_det, void* g_z, int64_t rows, int32_t D, int32_t inverse,
                              void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_to_interval_backward: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_to_interval_backward", dtype)) return rc;
     if (rows < 0 || D < 1) return fail(TNF_EINVAL, "tnf_to_interval_backward: rows=%lld D=%d", (long long)rows, D);
     if (rows == 0) return TNF_OK;
     if (!z || !consts || !g_z_out || !g_log_det || !g_z)
@@ -769,7 +757,7 @@ int tnf_to_interval_backward(int32_t dtype, const void* z, const float* consts, 
 
 int tnf_to_simplex(int32_t dtype, const void* z, void* z_out, void* log_det, int64_t rows, int32_t D_in,
                    int32_t D_attr, void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_to_simplex: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_to_simplex", dtype)) return rc;
     if (rows < 0 || D_in < 1 || D_attr < 1)
         return fail(TNF_EINVAL, "tnf_to_simplex: rows=%lld D_in=%d D_attr=%d", (long long)rows, D_in, D_attr);
     if (rows == 0) return TNF_OK;
@@ -779,7 +767,7 @@ int tnf_to_simplex(int32_t dtype, const void* z, void* z_out, void* log_det, int
 
 int tnf_to_simplex_backward(int32_t dtype, const void* z, const void* g_z_out, const void* g_log_det, void* g_z,
                             int64_t rows, int32_t D_in, int32_t D_attr, void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_to_simplex_backward: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_to_simplex_backward", dtype)) return rc;
     if (rows < 0 || D_in < 1 || D_attr < 1)
         return fail(TNF_EINVAL, "tnf_to_simplex_backward: rows=%lld D_in=%d D_attr=%d", (long long)rows, D_in, D_attr);
     if (rows == 0) return TNF_OK;
@@ -789,7 +777,7 @@ int tnf_to_simplex_backward(int32_t dtype, const void* z, const void* g_z_out, c
 
 // ---- exponential families (expfam_kernels.hip) ----
 static int ef_check(const char* fn, int32_t dtype, int32_t family, int32_t D) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "%s: dtype %d", fn, dtype);
+    if (int rc = check_dtype(fn, dtype)) return rc;
     if (family != TNF_EF_MVN && family != TNF_EF_DIRICHLET) return fail(TNF_EINVAL, "%s: family %d", fn, family);
     if (D < 1) return fail(TNF_EINVAL, "%s: D=%d must be positive", fn, D);
     if (D > TNF_EF_MAX_D) return fail(TNF_EUNSUPPORTED, "%s: D=%d exceeds %d", fn, D, TNF_EF_MAX_D);
@@ -861,15 +849,14 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
     if (g_eta && M > 0) {
         const int64_t need = ef_dot_bwd_workspace(family, M, N, D);
         if (need < 0) return fail(TNF_EUNSUPPORTED, "%s: no g_eta kernel for D=%d", fn, D);
-        if (!workspace || workspace_bytes < need)
-            return fail(TNF_EWORKSPACE, "%s: workspace %lld B < %lld B", fn, (long long)workspace_bytes, (long long)need);
+        if (int rc = check_workspace(fn, workspace, workspace_bytes, need)) return rc;
     }
     return launch_ef_dot_backward(dtype, family, z, eta, g_out, g_z, g_eta, M, N, D, ld_eta, workspace, as_stream(stream));
 }
 
 int tnf_base_log_density_f64(int32_t dtype, const void* omega, double* out, int64_t rows, int32_t D,
                              void* stream) {
-    if (dtype != TNF_F32 && dtype != TNF_F64) return fail(TNF_EINVAL, "tnf_base_log_density_f64: dtype %d", dtype);
+    if (int rc = check_dtype("tnf_base_log_density_f64", dtype)) return rc;
     if (rows < 0 || D < 1) return fail(TNF_EINVAL, "tnf_base_log_density_f64: rows=%lld D=%d", (long long)rows, D);
     if (!omega || !out) return fail(TNF_EINVAL, "tnf_base_log_density_f64: NULL pointer");
     return launch_base_log_density(dtype, omega, out, rows, D, as_stream(stream));
@@ -904,9 +891,7 @@ static int flow_common_checks(const char* fn, int64_t M_z, int64_t M_p, int64_t 
     int rc = check_mnd(fn, M_z, M_p, N, D);
     if (rc) return rc;
     if (S < 1 || L < 1 || U < 1) return fail(TNF_EINVAL, "%s: S=%d L=%d U=%d", fn, S, L, U);
-    if (pstride < flow_layout(D, S, L, U).total)
-        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn,
-                    (long long)pstride, (long long)flow_layout(D, S, L, U).total);
+    if (int rc = check_flow_row(fn, pstride, D, S, L, U)) return rc;
     if (!mfma_supported(D, L, U) && !wide_supported(D, L, U))
         return fail(TNF_EUNSUPPORTED, "%s: no fused kernel for D=%d L=%d U=%d (compose bijector-level calls)", fn, D, L, U);
     if (fusion == TNF_FUSE_AUTO) *use_fused = flow_fused_supported(D, S, L, U) ? 1 : 0;
@@ -918,10 +903,75 @@ static int flow_common_checks(const char* fn, int64_t M_z, int64_t M_p, int64_t 
     else return fail(TNF_EINVAL, "%s: fusion %d", fn, fusion);
     const int64_t M = M_z > M_p ? M_z : M_p;
     const FlowWs w = flow_ws(M, N, D, S, L, U);
-    const int64_t need = *use_fused ? w.zbuf : w.total;
-    if (!ws || ws_bytes < need)
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes, (long long)need);
-    return TNF_OK;
+    return check_workspace(fn, ws, ws_bytes, *use_fused ? w.zbuf : w.total);
+}
+
+// ---- which kernel family a coupling-flow call runs --------------------------------------------------------------------
+// The one place TNF_OPT_FLOW_VARIANT (fv), TNF_OPT_LAYER_VARIANT (lv) and, for these entries, TNF_OPT_OPERAND_PREC are
+// interpreted.  Pure host logic: no HIP call, no workspace access; a refusal leaves its message behind (fail()) and
+// its code in `rc`, before anything is launched.  `fused`: the whole flow in one launch (flow_common_checks resolved
+// TNF_FUSE_AUTO; always set for the reversible-training forward), narrow: mfma_supported(D, L, U).  First match wins:
+//
+//   inverse (tnf_flow_log_prob[_diag]_f32)
+//     bf16 operands                         the range kernel, all 2S layers in one launch when fused, else one layer per
+//                                           launch; EUNSUPPORTED where flow_range2_supported says no (every wide shape)
+//     support layer, but neither (fused, fv >= 10) nor (not fused, narrow, lv >= 10, range kernel)    EUNSUPPORTED
+//     fused, fv == 20, flow_fused3 fits     flow_fused3
+//     fused, fv 10 or 20, flow_fused2 fits  flow_fused2        (so 20 falls back to flow_fused2, then to flow_fused_f16)
+//     fused, fv >= 10                       flow_fused_f16, variant fv
+//     not fused, narrow, lv >= 10           flow_range2 chain, max(lv - 10, 1) layers per launch
+//     fused                                 fp32 whole-flow kernel (it reads fv 0 .. 5 as its launch geometry)
+//     narrow / wide                         fp32-MFMA per-layer chain / wide per-layer chain
+//
+//   reversible forward (tnf_flow_log_prob_fwd_rev_f32): the fused rows above, without the fp32 arm -- fv below 10 runs
+//   flow_fused_f16 as variant 10.
+//
+//   sampling (tnf_flow_forward[_logq]_f32): the same table, except that it ignores the operand precision (no bf16 arm),
+//   has no flow_fused3, fuses a support layer only into the whole-flow f16 kernels (its range chain takes none), runs
+//   the range chain at one layer per launch whatever lv - 10 says, and writes log_q only from flow_fused2: every later
+//   arm is EUNSUPPORTED for a log_q call.  The support-layer refusal comes before the log_q refusal.
+enum FlowDirection { FLOW_INVERSE, FLOW_SAMPLING, FLOW_REV_FORWARD };
+enum FlowFamily {
+    FLOW_REFUSED, FLOW_BF16_RANGE, FLOW_FUSED3, FLOW_FUSED2, FLOW_FUSED_F16, FLOW_RANGE2_CHAIN, FLOW_FP32_WHOLE,
+    FLOW_FP32_LAYERS, FLOW_WIDE_LAYERS
+};
+struct FlowChoice {
+    FlowFamily family;
+    int per_launch;  // layers per launch of the two range-kernel arms
+    int variant;     // of flow_fused_f16
+    int rc;          // FLOW_REFUSED: the code to return
+};
+struct FlowOptions {
+    int prec, fv, lv;
+};
+static FlowOptions flow_options() { return {g_operand_prec, g_flow_variant, g_layer_variant}; }  // the calling thread's
+
+static FlowChoice select_flow_kernel(const char* fn, FlowDirection dir, bool fused, int D, int S, int L, int U, bool support,
+                                     bool log_q, int fusion, const FlowOptions& opt) {
+    const int prec = opt.prec, fv = opt.fv, lv = opt.lv;
+    FlowChoice c = {FLOW_REFUSED, 1, fv >= 10 ? fv : 10, TNF_OK};
+    const bool narrow = mfma_supported(D, L, U);
+    if (prec == 1 && dir != FLOW_SAMPLING) {
+        c.per_launch = fused ? 2 * S : 1;
+        if (flow_range2_supported(D, L, U, c.per_launch)) c.family = FLOW_BF16_RANGE;
+        else c.rc = fail(TNF_EUNSUPPORTED, "%s: no bf16-operand kernel for D=%d S=%d L=%d U=%d", fn, D, S, L, U);
+        return c;
+    }
+    const bool f16 = fused && (fv >= 10 || dir == FLOW_REV_FORWARD);  // these build their own (split-f16) images
+    const bool chain2 = !fused && narrow && lv >= 10 && flow_range2_supported(D, L, U, 1);
+    if (support && !f16 && !(chain2 && dir == FLOW_INVERSE))
+        c.rc = fail(TNF_EUNSUPPORTED, "%s: a fused support layer needs the whole-flow kernel", fn);
+    else if (f16 && fv == 20 && dir != FLOW_SAMPLING && flow_fused3_supported(D, S, L, U)) c.family = FLOW_FUSED3;
+    else if (f16 && (fv == 10 || fv == 20) && flow_fused2_supported(D, S, L, U)) c.family = FLOW_FUSED2;
+    else if (log_q)
+        c.rc = fail(TNF_EUNSUPPORTED, "tnf_flow_forward_logq_f32: only the default whole-flow kernel writes log_q "
+                                      "(D=%d S=%d L=%d U=%d, fusion %d)", D, S, L, U, fusion);
+    else if (f16) c.family = FLOW_FUSED_F16;
+    else if (chain2) {
+        c.family = FLOW_RANGE2_CHAIN;
+        if (dir == FLOW_INVERSE && lv >= 11) c.per_launch = lv - 10;
+    } else c.family = fused ? FLOW_FP32_WHOLE : (narrow ? FLOW_FP32_LAYERS : FLOW_WIDE_LAYERS);
+    return c;
 }
 
 static int flow_log_prob_impl(const float* z, const float* params, const float* bn_mean,
@@ -940,49 +990,42 @@ static int flow_log_prob_impl(const float* z, const float* params, const float* 
         return fail(TNF_EINVAL, "tnf_flow_log_prob_f32: z / z0 must be 16-byte aligned");
     if (z0 == z) return fail(TNF_EINVAL, "tnf_flow_log_prob_f32: z0 must not alias z");
     if (N == 0) return TNF_OK;
+    const FlowChoice k = select_flow_kernel("tnf_flow_log_prob_f32", FLOW_INVERSE, use_fused != 0, D, S, L, U,
+                                            interval_consts != nullptr, false, fusion, flow_options());
     hipStream_t st = as_stream(stream);
     const int64_t M = M_z > M_p ? M_z : M_p;
     const FlowWs w = flow_ws(M, N, D, S, L, U);
-    char* wsb = reinterpret_cast<char*>(workspace);
-    float* fold = reinterpret_cast<float*>(wsb + w.fold);
-    float* ldc = reinterpret_cast<float*>(wsb + w.ldc);
-    float* images = reinterpret_cast<float*>(wsb + w.images);
-    const bool narrow = mfma_supported(D, L, U);
-    const int64_t img_floats = narrow ? mfma_image_floats(D, L) : wide_image_floats(D, L, U);
-    const bool f16 = use_fused && g_flow_variant >= 10;  // builds its own (split-f16) images
-    if (g_operand_prec == 1) {
-        // the bf16 experiment runs on the layer-range kernel: all 2S layers in one launch, or one layer per launch
-        if (!narrow || !flow_range2_supported(D, L, U, use_fused ? 2 * S : 1))
-            return fail(TNF_EUNSUPPORTED, "tnf_flow_log_prob_f32: no bf16-operand kernel for D=%d S=%d L=%d U=%d", D, S, L, U);
-        float* zb = z0 ? z0 : reinterpret_cast<float*>(wsb + w.zbuf);
-        float* lb = sum_log_det ? sum_log_det : reinterpret_cast<float*>(wsb + w.ldbuf);
-        return launch_flow_chain2(z, use_fused ? nullptr : zb, use_fused ? nullptr : lb, z0, sum_log_det, log_prob, M_z, M_p, N, D,
-                                  S, L, U, params, pstride, bn_mean, bn_alpha, interval_consts, nullptr,
-                                  use_fused ? 2 * S : 1, st, 1);
-    }
-    const bool chain2 = !use_fused && narrow && g_layer_variant >= 10 && flow_range2_supported(D, L, U, 1);
-    if (interval_consts && !f16 && !chain2)
-        return fail(TNF_EUNSUPPORTED, "tnf_flow_log_prob_f32: a fused support layer needs the whole-flow kernel");
-    if (f16 && g_flow_variant == 20 && flow_fused3_supported(D, S, L, U))  // 32-sample groups, 32x32x16 MFMAs (f16_tile3.h)
-        return launch_flow_fused3(z, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha,
-                                  interval_consts, exact_reruns, st);
-    if (f16 && (g_flow_variant == 10 || g_flow_variant == 20) && flow_fused2_supported(D, S, L, U))  // f16_tile2.h
-        return launch_flow_fused2(z, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha,
-                                  interval_consts, exact_reruns, st);
-    if (f16)  // ONE launch: the flow kernel builds its split-f16 operands and folds BN / Affine in its prologue
-        return launch_flow_fused_f16(z, nullptr, nullptr, nullptr, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U,
-                                     1, g_flow_variant, st, params, pstride, bn_mean, bn_alpha, interval_consts);
-    if (!use_fused && narrow && g_layer_variant >= 10 && flow_range2_supported(D, L, U, 1)) {
-        // default per-layer chain: the whole-flow kernel's tile code, ONE coupling layer per launch (flow_fused2.hip)
-        float* zb = z0 ? z0 : reinterpret_cast<float*>(wsb + w.zbuf);
-        float* lb = sum_log_det ? sum_log_det : reinterpret_cast<float*>(wsb + w.ldbuf);
-        return launch_flow_chain2(z, zb, lb, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean,
-                                  bn_alpha, interval_consts, exact_reruns, g_layer_variant >= 11 ? g_layer_variant - 10 : 1, st,
-                                  0, images);  // `images`: the workspace region that holds the prepared prologues
+    float* fold = ws_floats(workspace, w.fold);
+    float* ldc = ws_floats(workspace, w.ldc);
+    float* images = ws_floats(workspace, w.images);
+    // z / log-det scratch of the chains (the whole-flow workspace has none)
+    float* zbuf = use_fused ? nullptr : (z0 ? z0 : ws_floats(workspace, w.zbuf));
+    float* ldbuf = use_fused ? nullptr : (sum_log_det ? sum_log_det : ws_floats(workspace, w.ldbuf));
+    switch (k.family) {
+        case FLOW_REFUSED: return k.rc;
+        case FLOW_BF16_RANGE:  // the bf16 experiment runs on the layer-range kernel
+            return launch_flow_chain2(z, zbuf, ldbuf, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U, params, pstride,
+                                      bn_mean, bn_alpha, interval_consts, nullptr, k.per_launch, st, 1);
+        case FLOW_FUSED3:  // 32-sample groups, 32x32x16 MFMAs (f16_tile3.h)
+            return launch_flow_fused3(z, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean,
+                                      bn_alpha, interval_consts, exact_reruns, st);
+        case FLOW_FUSED2:  // f16_tile2.h
+            return launch_flow_fused2(z, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean,
+                                      bn_alpha, interval_consts, exact_reruns, st);
+        case FLOW_FUSED_F16:  // ONE launch: the flow kernel builds its split-f16 operands and folds BN / Affine in its prologue
+            return launch_flow_fused_f16(z, nullptr, nullptr, nullptr, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U,
+                                         1, k.variant, st, params, pstride, bn_mean, bn_alpha, interval_consts);
+        case FLOW_RANGE2_CHAIN:
+            // default per-layer chain: the whole-flow kernel's tile code, ONE coupling layer per launch (flow_fused2.hip)
+            return launch_flow_chain2(z, zbuf, ldbuf, z0, sum_log_det, log_prob, M_z, M_p, N, D, S, L, U, params, pstride,
+                                      bn_mean, bn_alpha, interval_consts, exact_reruns, k.per_launch, st, 0,
+                                      images);  // `images`: the workspace region that holds the prepared prologues
+        default: break;
     }
     // fp32-MFMA per-layer chain on the narrow shapes: in place from the second kernel on, each kernel storing only the
     // half it transforms (the folds are composed accordingly, flow_fold_kernel chain = 1)
-    const int chain = (!use_fused && narrow) ? 1 : 0;
+    const bool narrow = mfma_supported(D, L, U);
+    const int chain = k.family == FLOW_FP32_LAYERS ? 1 : 0;
     rc = launch_flow_prep(params, bn_mean, bn_alpha, fold, ldc, narrow ? images : nullptr, M_p, D, S, L, U, pstride, 1, st,
                           chain);
     if (rc) return rc;
@@ -990,26 +1033,22 @@ static int flow_log_prob_impl(const float* z, const float* params, const float* 
         rc = launch_wide_images(params, images, M_p, D, S, L, U, pstride, st);
         if (rc) return rc;
     }
-    if (use_fused)
+    if (k.family == FLOW_FP32_WHOLE)
         return launch_flow_fused(z, images, fold, ldc, z0, sum_log_det, log_prob, M_z, M_p, N, D, S,
                                  L, U, 1, st);
     // one launch per coupling layer, last forward layer first
-    float* zbuf = z0 ? z0 : reinterpret_cast<float*>(wsb + w.zbuf);
-    float* ldbuf = sum_log_det ? sum_log_det : reinterpret_cast<float*>(wsb + w.ldbuf);
     const FlowLayout fl = flow_layout(D, S, L, U);
+    const int64_t img_floats = narrow ? mfma_image_floats(D, L) : wide_image_floats(D, L, U);
     const int nl = 2 * S;
     for (int c = nl - 1; c >= 0; --c) {
-        MfmaLayerArgs a;
-        memset(&a, 0, sizeof(a));
+        const FlowLayerAt at = flow_layer_at(fl, c, S, D, images, img_floats);
+        MfmaLayerArgs a = {};
         const bool first = (c == nl - 1), last = (c == 0);
+        set_flow_layer(a, at, params, pstride, U);
         a.z = first ? z : zbuf;
         a.z_out = (last && !z0) ? nullptr : zbuf;
-        a.params = params + (c >> 1) * fl.stage + ((c & 1) ? fl.p_up : 0);
-        a.pstride = pstride;
-        a.image = images + (int64_t)c * img_floats;
-        a.image_stride = (int64_t)nl * img_floats;
-        a.pre = fold + (int64_t)c * 2 * D;
-        a.fold_stride = (int64_t)nl * 2 * D;
+        a.pre = fold + at.fold_off;
+        a.fold_stride = at.fold_stride;
         a.ld_in = first ? nullptr : ldbuf;
         a.ld_out = (last && !sum_log_det) ? nullptr : ldbuf;
         a.ld_sign = 1.f;
@@ -1017,7 +1056,7 @@ static int flow_log_prob_impl(const float* z, const float* params, const float* 
         a.add_ldc = last ? 1 : 0;
         a.log_prob = last ? log_prob : nullptr;
         a.Mz = first ? M_z : M; a.Mp = M_p; a.N = N;
-        a.D = D; a.L = L; a.U = U; a.upper = (c & 1) ? 0 : 1; a.inverse = 1;
+        a.D = D; a.L = L; a.inverse = 1;
         a.skip_cond_store = (chain && !first && !(last && z0)) ? 1 : 0;
         rc = narrow ? launch_coupling_mfma(a, st) : launch_coupling_wide(a, st);
         if (rc) return rc;
@@ -1065,46 +1104,41 @@ static TrainWs train_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L) {
 }
 
 int64_t tnf_flow_train_workspace_bytes(int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t S, int32_t L, int32_t U) {
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0 || S < 1)
-        return fail(TNF_EINVAL, "tnf_flow_train_workspace_bytes: M=%lld M_p=%lld N=%lld S=%d", (long long)M,
-                    (long long)M_p, (long long)N, S);
+    if (int rc = check_batch_stages("tnf_flow_train_workspace_bytes", M, M_p, N, S)) return rc;
     if (!mfma_supported(D, L, U))
         return fail(TNF_EUNSUPPORTED, "tnf_flow_train_workspace_bytes: no training kernels for D=%d L=%d U=%d", D, L, U);
     return train_ws(M, M_p, N, D, S, L).total;
 }
 
-static int train_checks(const char* fn, int64_t M, int64_t M_p, int64_t N, int D, int S, int L, int U,
-                        int64_t pstride, const void* ws, int64_t ws_bytes) {
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0 || S < 1)
-        return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld S=%d", fn, (long long)M, (long long)M_p, (long long)N, S);
-    if (!mfma_supported(D, L, U))
-        return fail(TNF_EUNSUPPORTED, "%s: no training kernels for D=%d L=%d U=%d", fn, D, L, U);
-    if (pstride < flow_layout(D, S, L, U).total)
-        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride,
-                    (long long)flow_layout(D, S, L, U).total);
-    if (!ws || ws_bytes < train_ws(M, M_p, N, D, S, L).total)
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes,
-                    (long long)train_ws(M, M_p, N, D, S, L).total);
-    return TNF_OK;
+// the chains that exist for the narrow shapes only (training pair, batch-statistics forward and its training pair): batch,
+// shape, more than one row where batch statistics are taken, parameter row
+static int narrow_chain_checks(const char* fn, int64_t M, int64_t M_p, int64_t N, int D, int S, int L, int U, bool batch_stats,
+                               int64_t pstride) {
+    int rc = check_batch_stages(fn, M, M_p, N, S);
+    if (rc) return rc;
+    if (!mfma_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "%s: no kernel for D=%d L=%d U=%d", fn, D, L, U);
+    if (batch_stats && M * N < 2) return fail(TNF_EINVAL, "%s: batch statistics need more than one row", fn);
+    return check_flow_row(fn, pstride, D, S, L, U);
 }
 
 int tnf_flow_log_prob_fwd_f32(const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
                               float* log_prob, float* states, int64_t M, int64_t M_p, int64_t N, int32_t D,
                               int32_t S, int32_t L, int32_t U, int64_t pstride, void* workspace,
                               int64_t workspace_bytes, void* stream) {
-    int rc = train_checks("tnf_flow_log_prob_fwd_f32", M, M_p, N, D, S, L, U, pstride, workspace, workspace_bytes);
+    const char* fn = "tnf_flow_log_prob_fwd_f32";
+    int rc = narrow_chain_checks(fn, M, M_p, N, D, S, L, U, false, pstride);
+    if (!rc) rc = check_workspace(fn, workspace, workspace_bytes, train_ws(M, M_p, N, D, S, L).total);
     if (rc) return rc;
     if (!z || !params || !bn_mean || !bn_alpha || !log_prob || !states)
-        return fail(TNF_EINVAL, "tnf_flow_log_prob_fwd_f32: NULL pointer");
-    if (!aligned16(z) || !aligned16(states)) return fail(TNF_EINVAL, "tnf_flow_log_prob_fwd_f32: z / states must be 16-byte aligned");
+        return fail(TNF_EINVAL, "%s: NULL pointer", fn);
+    if (!aligned16(z) || !aligned16(states)) return fail(TNF_EINVAL, "%s: z / states must be 16-byte aligned", fn);
     if (N == 0) return TNF_OK;
     hipStream_t st = as_stream(stream);
     const TrainWs w = train_ws(M, M_p, N, D, S, L);
-    char* wsb = reinterpret_cast<char*>(workspace);
-    float* fold = reinterpret_cast<float*>(wsb + w.fold);
-    float* ldc = reinterpret_cast<float*>(wsb + w.ldc);
-    float* images = reinterpret_cast<float*>(wsb + w.images);
-    float* ldbuf = reinterpret_cast<float*>(wsb + w.ldbuf);
+    float* fold = ws_floats(workspace, w.fold);
+    float* ldc = ws_floats(workspace, w.ldc);
+    float* images = ws_floats(workspace, w.images);
+    float* ldbuf = ws_floats(workspace, w.ldbuf);
     rc = launch_flow_prep(params, bn_mean, bn_alpha, fold, ldc, images, M_p, D, S, L, U, pstride, 1, st);
     if (rc) return rc;
     const FlowLayout fl = flow_layout(D, S, L, U);
@@ -1112,17 +1146,14 @@ int tnf_flow_log_prob_fwd_f32(const float* z, const float* params, const float* 
     const int nl = 2 * S;
     const int64_t plane = M * N * D;
     for (int c = nl - 1; c >= 0; --c) {
-        MfmaLayerArgs a;
-        memset(&a, 0, sizeof(a));
+        const FlowLayerAt at = flow_layer_at(fl, c, S, D, images, img_floats);
+        MfmaLayerArgs a = {};
         const bool first = (c == nl - 1), last = (c == 0);
+        set_flow_layer(a, at, params, pstride, U);
         a.z = first ? z : states + (int64_t)c * plane;       // states[c] = input of layer kernel c
         a.z_out = last ? nullptr : states + (int64_t)(c - 1) * plane;
-        a.params = params + (c >> 1) * fl.stage + ((c & 1) ? fl.p_up : 0);
-        a.pstride = pstride;
-        a.image = images + (int64_t)c * img_floats;
-        a.image_stride = (int64_t)nl * img_floats;
-        a.pre = fold + (int64_t)c * 2 * D;
-        a.fold_stride = (int64_t)nl * 2 * D;
+        a.pre = fold + at.fold_off;
+        a.fold_stride = at.fold_stride;
         a.ld_in = first ? nullptr : ldbuf;
         a.ld_out = last ? nullptr : ldbuf;
         a.ld_sign = 1.f;
@@ -1130,7 +1161,7 @@ int tnf_flow_log_prob_fwd_f32(const float* z, const float* params, const float* 
         a.add_ldc = last ? 1 : 0;
         a.log_prob = last ? log_prob : nullptr;
         a.Mz = M; a.Mp = M_p; a.N = N;
-        a.D = D; a.L = L; a.U = U; a.upper = (c & 1) ? 0 : 1; a.inverse = 1;
+        a.D = D; a.L = L; a.inverse = 1;
         a.gate = g_launch_gate;
         rc = launch_coupling_mfma(a, st);
         if (rc) return rc;
@@ -1143,27 +1174,27 @@ int tnf_flow_log_prob_bwd_f32(const float* z, const float* states, const float* 
                               int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t S, int32_t L, int32_t U,
                               int64_t pstride, int64_t gpstride, void* workspace, int64_t workspace_bytes,
                               void* stream) {
-    int rc = train_checks("tnf_flow_log_prob_bwd_f32", M, M_p, N, D, S, L, U, pstride, workspace, workspace_bytes);
+    const char* fn = "tnf_flow_log_prob_bwd_f32";
+    int rc = narrow_chain_checks(fn, M, M_p, N, D, S, L, U, false, pstride);
+    if (!rc) rc = check_workspace(fn, workspace, workspace_bytes, train_ws(M, M_p, N, D, S, L).total);
     if (rc) return rc;
     if (!z || !states || !params || !bn_mean || !bn_alpha || !g_log_prob || !g_z || !g_params)
-        return fail(TNF_EINVAL, "tnf_flow_log_prob_bwd_f32: NULL pointer");
-    if (gpstride < flow_layout(D, S, L, U).total) return fail(TNF_EINVAL, "tnf_flow_log_prob_bwd_f32: g_params row too short");
+        return fail(TNF_EINVAL, "%s: NULL pointer", fn);
+    if (gpstride < flow_layout(D, S, L, U).total) return fail(TNF_EINVAL, "%s: g_params row too short", fn);
     if (N == 0) return TNF_OK;
     hipStream_t st = as_stream(stream);
     const TrainWs w = train_ws(M, M_p, N, D, S, L);
-    char* wsb = reinterpret_cast<char*>(workspace);
-    float* fold = reinterpret_cast<float*>(wsb + w.fold);
-    float* ldc = reinterpret_cast<float*>(wsb + w.ldc);
-    float* images = reinterpret_cast<float*>(wsb + w.images);
-    float* gfold = reinterpret_cast<float*>(wsb + w.gfold);
-    float* gbuf[2] = {reinterpret_cast<float*>(wsb + w.gbuf),
-                      reinterpret_cast<float*>(wsb + w.gbuf + round16(M * N * D * (int64_t)sizeof(float)))};
+    float* fold = ws_floats(workspace, w.fold);
+    float* ldc = ws_floats(workspace, w.ldc);
+    float* images = ws_floats(workspace, w.images);
+    float* gfold = ws_floats(workspace, w.gfold);
+    float* gbuf[2] = {ws_floats(workspace, w.gbuf), ws_floats(workspace, w.gbuf + round16(M * N * D * (int64_t)sizeof(float)))};
     rc = launch_flow_prep(params, bn_mean, bn_alpha, fold, ldc, images, M_p, D, S, L, U, pstride, 1, st);
     if (rc) return rc;
     float* glp_sum = gfold + M_p * 2 * S * 2 * D;
     unsigned* gmaxw = reinterpret_cast<unsigned*>(glp_sum + M_p);
     if (hipMemsetAsync(gfold, 0, (size_t)(M_p * 2 * S * 2 * D + M_p + 1) * sizeof(float), st) != hipSuccess)
-        return fail(TNF_ELAUNCH, "tnf_flow_log_prob_bwd_f32: memset failed");
+        return fail(TNF_ELAUNCH, "%s: memset failed", fn);
     rc = launch_gmax(g_log_prob, M * N, gmaxw, st);
     if (rc) return rc;
     const FlowLayout fl = flow_layout(D, S, L, U);
@@ -1171,24 +1202,20 @@ int tnf_flow_log_prob_bwd_f32(const float* z, const float* states, const float* 
     const int nl = 2 * S;
     const int64_t plane = M * N * D;
     for (int c = 0; c < nl; ++c) {
-        BwdArgs a;
-        memset(&a, 0, sizeof(a));
-        const int64_t poff = (c >> 1) * fl.stage + ((c & 1) ? fl.p_up : 0);
+        const FlowLayerAt at = flow_layer_at(fl, c, S, D, images, img_floats);
+        BwdArgs a = {};
+        set_flow_layer(a, at, params, pstride, U);
         a.z = (c == nl - 1) ? z : states + (int64_t)c * plane;
-        a.params = params + poff;
         a.g_zout = (c == 0) ? nullptr : gbuf[(c - 1) & 1];
         a.g_ld = g_log_prob;
         a.ld_scale = -1.f;  // log_prob = base - sum of the layers' log-dets
         a.g_z = (c == nl - 1) ? g_z : gbuf[c & 1];
-        a.g_params = g_params + poff;
+        a.g_params = g_params + at.poff;
+        a.gpstride = gpstride;
         a.M = M; a.Mp = M_p; a.N = N;
-        a.pstride = pstride; a.gpstride = gpstride;
-        a.U = U; a.upper = (c & 1) ? 0 : 1;
-        a.image = images + (int64_t)c * img_floats;
-        a.image_stride = (int64_t)nl * img_floats;
-        a.fold = fold + (int64_t)c * 2 * D;
-        a.g_fold = gfold + (int64_t)c * 2 * D;
-        a.fold_stride = (int64_t)nl * 2 * D;
+        a.fold = fold + at.fold_off;
+        a.g_fold = gfold + at.fold_off;
+        a.fold_stride = at.fold_stride;
         a.g_lp = (c == 0) ? g_log_prob : nullptr;
         a.glp_sum = glp_sum;
         a.gmax = gmaxw;
@@ -1208,23 +1235,17 @@ int tnf_flow_train_rev_supported(int32_t D, int32_t S, int32_t L, int32_t U) {
 }
 
 int64_t tnf_flow_train_rev_workspace_bytes(int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t S, int32_t L, int32_t U) {
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0)
-        return fail(TNF_EINVAL, "tnf_flow_train_rev_workspace_bytes: M=%lld M_p=%lld N=%lld", (long long)M, (long long)M_p,
-                    (long long)N);
+    if (int rc = check_batch("tnf_flow_train_rev_workspace_bytes", M, M_p, N)) return rc;
     if (!tnf_flow_train_rev_supported(D, S, L, U))
         return fail(TNF_EUNSUPPORTED, "tnf_flow_train_rev_workspace_bytes: D=%d S=%d L=%d U=%d", D, S, L, U);
     return flow_train_rev_workspace(M, M_p, N, D, S, L, U);
 }
 
 static int rev_checks(const char* fn, int64_t M, int64_t M_p, int64_t N, int D, int S, int L, int U, int64_t pstride) {
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0)
-        return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld", fn, (long long)M, (long long)M_p, (long long)N);
+    if (int rc = check_batch(fn, M, M_p, N)) return rc;
     if (!tnf_flow_train_rev_supported(D, S, L, U))
         return fail(TNF_EUNSUPPORTED, "%s: no reversible training kernels for D=%d S=%d L=%d U=%d", fn, D, S, L, U);
-    if (pstride < flow_layout(D, S, L, U).total)
-        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride,
-                    (long long)flow_layout(D, S, L, U).total);
-    return TNF_OK;
+    return check_flow_row(fn, pstride, D, S, L, U);
 }
 
 int tnf_flow_log_prob_fwd_rev_f32(const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
@@ -1236,21 +1257,24 @@ int tnf_flow_log_prob_fwd_rev_f32(const float* z, const float* params, const flo
     if (!z || !params || !bn_mean || !bn_alpha || !log_prob || !z0)
         return fail(TNF_EINVAL, "tnf_flow_log_prob_fwd_rev_f32: NULL pointer");
     if (!aligned16(z) || !aligned16(z0)) return fail(TNF_EINVAL, "tnf_flow_log_prob_fwd_rev_f32: z / z0 must be 16-byte aligned");
-    if (g_operand_prec == 1) {  // the bf16 experiment: forward activations from bf16 operands (the backward stays split-f16)
-        if (!flow_range2_supported(D, L, U, 2 * S))
-            return fail(TNF_EUNSUPPORTED, "tnf_flow_log_prob_fwd_rev_f32: no bf16-operand kernel for D=%d S=%d L=%d U=%d", D, S, L, U);
-        return launch_flow_chain2(z, nullptr, nullptr, z0, nullptr, log_prob, M, M_p, N, D, S, L, U, params, pstride, bn_mean,
-                                  bn_alpha, nullptr, nullptr, 2 * S, as_stream(stream), 1);
+    const FlowChoice k = select_flow_kernel("tnf_flow_log_prob_fwd_rev_f32", FLOW_REV_FORWARD, true, D, S, L, U, false, false,
+                                            TNF_FUSE_FLOW, flow_options());
+    hipStream_t st = as_stream(stream);
+    switch (k.family) {
+        case FLOW_BF16_RANGE:  // the bf16 experiment: forward activations from bf16 operands (the backward stays split-f16)
+            return launch_flow_chain2(z, nullptr, nullptr, z0, nullptr, log_prob, M, M_p, N, D, S, L, U, params, pstride,
+                                      bn_mean, bn_alpha, nullptr, nullptr, k.per_launch, st, 1);
+        case FLOW_FUSED3:
+            return launch_flow_fused3(z, z0, nullptr, log_prob, M, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha,
+                                      nullptr, nullptr, st);
+        case FLOW_FUSED2:
+            return launch_flow_fused2(z, z0, nullptr, log_prob, M, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha,
+                                      nullptr, nullptr, st);
+        case FLOW_FUSED_F16:
+            return launch_flow_fused_f16(z, nullptr, nullptr, nullptr, z0, nullptr, log_prob, M, M_p, N, D, S, L, U, 1,
+                                         k.variant, st, params, pstride, bn_mean, bn_alpha, nullptr);
+        default: return k.rc;  // FLOW_REFUSED: this direction has no other arm
     }
-    if (g_flow_variant == 20 && flow_fused3_supported(D, S, L, U))
-        return launch_flow_fused3(z, z0, nullptr, log_prob, M, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha, nullptr,
-                                  nullptr, as_stream(stream));
-    if ((g_flow_variant == 10 || g_flow_variant == 20) && flow_fused2_supported(D, S, L, U))
-        return launch_flow_fused2(z, z0, nullptr, log_prob, M, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha, nullptr,
-                                  nullptr, as_stream(stream));
-    return launch_flow_fused_f16(z, nullptr, nullptr, nullptr, z0, nullptr, log_prob, M, M_p, N, D, S, L, U, 1,
-                                 g_flow_variant >= 10 ? g_flow_variant : 10, as_stream(stream), params, pstride, bn_mean,
-                                 bn_alpha, nullptr);
 }
 
 int tnf_flow_log_prob_bwd_rev_f32(const float* z0, const float* params, const float* bn_mean, const float* bn_alpha,
@@ -1267,9 +1291,8 @@ int tnf_flow_log_prob_bwd_rev_f32(const float* z0, const float* params, const fl
         return fail(TNF_EINVAL, "tnf_flow_log_prob_bwd_rev_f32: z0 / g_z must be 16-byte aligned");
     if (gpstride < flow_layout(D, S, L, U).total)
         return fail(TNF_EINVAL, "tnf_flow_log_prob_bwd_rev_f32: g_params row too short");
-    if (!workspace || workspace_bytes < flow_train_rev_workspace(M, M_p, N, D, S, L, U))
-        return fail(TNF_EWORKSPACE, "tnf_flow_log_prob_bwd_rev_f32: workspace %lld < %lld", (long long)workspace_bytes,
-                    (long long)flow_train_rev_workspace(M, M_p, N, D, S, L, U));
+    rc = check_workspace("tnf_flow_log_prob_bwd_rev_f32", workspace, workspace_bytes, flow_train_rev_workspace(M, M_p, N, D, S, L, U));
+    if (rc) return rc;
     return launch_flow_bwd_rev(z0, params, bn_mean, bn_alpha, g_log_prob, g_z, g_params, M, M_p, N, D, S, L, U, pstride,
                                gpstride, workspace, overflow, as_stream(stream));
 }
@@ -1286,20 +1309,14 @@ int tnf_flow_forward_batch_f32(const float* omega, const float* params, float* z
                                int32_t S, int32_t L, int32_t U, int64_t pstride, float eps, void* workspace,
                                int64_t workspace_bytes, void* stream) {
     const char* fn = "tnf_flow_forward_batch_f32";
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0 || S < 1)
-        return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld S=%d", fn, (long long)M, (long long)M_p, (long long)N, S);
-    if (!mfma_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "%s: no kernel for D=%d L=%d U=%d", fn, D, L, U);
-    if (M * N < 2) return fail(TNF_EINVAL, "%s: batch statistics need more than one row", fn);
-    if (pstride < flow_layout(D, S, L, U).total)
-        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride,
-                    (long long)flow_layout(D, S, L, U).total);
+    int rc = narrow_chain_checks(fn, M, M_p, N, D, S, L, U, true, pstride);
+    if (rc) return rc;
     if (!omega || !params || !z_out || !sum_log_det || !bn_mean_out || !bn_alpha_out || !workspace)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
     if (!aligned16(omega) || !aligned16(z_out)) return fail(TNF_EINVAL, "%s: omega / z_out must be 16-byte aligned", fn);
     if (z_out == omega) return fail(TNF_EINVAL, "%s: z_out must not alias omega", fn);
-    if (workspace_bytes < flow_forward_batch_workspace(M_p, D, S, L))
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)workspace_bytes,
-                    (long long)flow_forward_batch_workspace(M_p, D, S, L));
+    rc = check_workspace(fn, workspace, workspace_bytes, flow_forward_batch_workspace(M_p, D, S, L));
+    if (rc) return rc;
     return launch_flow_forward_batch(omega, params, z_out, sum_log_det, bn_mean_out, bn_alpha_out, M, M_p, N, D, S, L, U,
                                      pstride, eps, workspace, as_stream(stream));
 }
@@ -1310,13 +1327,8 @@ static int fb_step_checks(const char* fn, int64_t M_p, int D, int S, int L, int 
                           int64_t ws_bytes) {
     if (M_p < 1 || S < 1) return fail(TNF_EINVAL, "%s: M_p=%lld S=%d", fn, (long long)M_p, S);
     if (!mfma_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "%s: no kernel for D=%d L=%d U=%d", fn, D, L, U);
-    if (pstride < flow_layout(D, S, L, U).total)
-        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride,
-                    (long long)flow_layout(D, S, L, U).total);
-    if (!ws || ws_bytes < flow_forward_batch_workspace(M_p, D, S, L))
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes,
-                    (long long)flow_forward_batch_workspace(M_p, D, S, L));
-    return TNF_OK;
+    if (int rc = check_flow_row(fn, pstride, D, S, L, U)) return rc;
+    return check_workspace(fn, ws, ws_bytes, flow_forward_batch_workspace(M_p, D, S, L));
 }
 
 int tnf_flow_forward_batch_begin_f32(const float* params, int64_t M_p, int32_t D, int32_t S, int32_t L, int32_t U,
@@ -1335,7 +1347,8 @@ int tnf_flow_forward_batch_layer_f32(int32_t layer, const float* z_in, const flo
     const char* fn = "tnf_flow_forward_batch_layer_f32";
     int rc = fb_step_checks(fn, M_p, D, S, L, U, pstride, workspace, workspace_bytes);
     if (rc) return rc;
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0) return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld", fn, (long long)M, (long long)M_p, (long long)N);
+    rc = check_batch(fn, M, M_p, N);
+    if (rc) return rc;
     if (layer < 0 || layer >= 2 * S) return fail(TNF_EINVAL, "%s: layer %d of %d", fn, layer, 2 * S);
     if (!params || !moments || (N > 0 && (!z_in || !z_out || !sum_log_det))) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
     if (!aligned16(z_in) || !aligned16(z_out) || (reinterpret_cast<uintptr_t>(moments) & 7))
@@ -1360,7 +1373,7 @@ int tnf_flow_forward_batch_fold_f32(int32_t layer, const float* params, const do
 int tnf_flow_forward_batch_end_f32(float* z_out, float* sum_log_det, int64_t M, int64_t M_p, int64_t N, int32_t D,
                                    int32_t S, int32_t L, void* workspace, int64_t workspace_bytes, void* stream) {
     const char* fn = "tnf_flow_forward_batch_end_f32";
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0 || D < 2 || S < 1 || L < 1)
+    if (bad_batch(M, M_p, N) || D < 2 || S < 1 || L < 1)
         return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld D=%d", fn, (long long)M, (long long)M_p, (long long)N, D);
     if (!workspace || workspace_bytes < flow_forward_batch_workspace(M_p, D, S, L))
         return fail(TNF_EWORKSPACE, "%s: workspace too small", fn);
@@ -1370,25 +1383,10 @@ int tnf_flow_forward_batch_end_f32(float* z_out, float* sum_log_det, int64_t M, 
 
 // ... and the same stack under autograd (sampling-based objectives): forward keeps every coupling layer's output
 int64_t tnf_flow_forward_train_workspace_bytes(int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t S, int32_t L) {
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0 || D < 2 || S < 1 || L < 1)
+    if (bad_batch(M, M_p, N) || D < 2 || S < 1 || L < 1)
         return fail(TNF_EINVAL, "tnf_flow_forward_train_workspace_bytes: M=%lld M_p=%lld N=%lld D=%d S=%d L=%d",
                     (long long)M, (long long)M_p, (long long)N, D, S, L);
     return flow_forward_train_workspace(M, M_p, N, D, S, L);
-}
-
-static int fwd_train_checks(const char* fn, int64_t M, int64_t M_p, int64_t N, int D, int S, int L, int U, int64_t pstride,
-                            const void* ws, int64_t ws_bytes) {
-    if (M < 1 || (M_p != 1 && M_p != M) || N < 0 || S < 1)
-        return fail(TNF_EINVAL, "%s: M=%lld M_p=%lld N=%lld S=%d", fn, (long long)M, (long long)M_p, (long long)N, S);
-    if (!mfma_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "%s: no kernel for D=%d L=%d U=%d", fn, D, L, U);
-    if (M * N < 2) return fail(TNF_EINVAL, "%s: batch statistics need more than one row", fn);
-    if (pstride < flow_layout(D, S, L, U).total)
-        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride,
-                    (long long)flow_layout(D, S, L, U).total);
-    if (!ws || ws_bytes < flow_forward_train_workspace(M, M_p, N, D, S, L))
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes,
-                    (long long)flow_forward_train_workspace(M, M_p, N, D, S, L));
-    return TNF_OK;
 }
 
 int tnf_flow_forward_train_fwd_f32(const float* omega, const float* params, float* z_out, float* sum_log_det,
@@ -1396,7 +1394,8 @@ int tnf_flow_forward_train_fwd_f32(const float* omega, const float* params, floa
                                    int64_t M_p, int64_t N, int32_t D, int32_t S, int32_t L, int32_t U, int64_t pstride,
                                    float eps, void* workspace, int64_t workspace_bytes, void* stream) {
     const char* fn = "tnf_flow_forward_train_fwd_f32";
-    int rc = fwd_train_checks(fn, M, M_p, N, D, S, L, U, pstride, workspace, workspace_bytes);
+    int rc = narrow_chain_checks(fn, M, M_p, N, D, S, L, U, true, pstride);
+    if (!rc) rc = check_workspace(fn, workspace, workspace_bytes, flow_forward_train_workspace(M, M_p, N, D, S, L));
     if (rc) return rc;
     if (!omega || !params || !z_out || !sum_log_det || !states || !folds || !bn_mean_out || !bn_alpha_out)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
@@ -1412,7 +1411,8 @@ int tnf_flow_forward_train_bwd_f32(const float* omega, const float* params, cons
                                    int32_t L, int32_t U, int64_t pstride, int64_t gpstride, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
     const char* fn = "tnf_flow_forward_train_bwd_f32";
-    int rc = fwd_train_checks(fn, M, M_p, N, D, S, L, U, pstride, workspace, workspace_bytes);
+    int rc = narrow_chain_checks(fn, M, M_p, N, D, S, L, U, true, pstride);
+    if (!rc) rc = check_workspace(fn, workspace, workspace_bytes, flow_forward_train_workspace(M, M_p, N, D, S, L));
     if (rc) return rc;
     if (!omega || !params || !states || !folds || !bn_mean || !bn_alpha || !g_z || !g_sum_log_det || !g_params)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
@@ -1440,62 +1440,58 @@ static int flow_forward_impl(const float* omega, const float* params, const floa
         return fail(TNF_EINVAL, "tnf_flow_forward_f32: omega / z_out must be 16-byte aligned");
     if (z_out == omega) return fail(TNF_EINVAL, "tnf_flow_forward_f32: z_out must not alias omega");
     if (N == 0) return TNF_OK;
+    const FlowChoice k = select_flow_kernel("tnf_flow_forward_f32", FLOW_SAMPLING, use_fused != 0, D, S, L, U,
+                                            interval_consts != nullptr, log_q != nullptr, fusion, flow_options());
     hipStream_t st = as_stream(stream);
     const int64_t M = M_z > M_p ? M_z : M_p;
     const FlowWs w = flow_ws(M, N, D, S, L, U);
-    char* wsb = reinterpret_cast<char*>(workspace);
-    float* fold = reinterpret_cast<float*>(wsb + w.fold);
-    float* ldc = reinterpret_cast<float*>(wsb + w.ldc);
-    float* images = reinterpret_cast<float*>(wsb + w.images);
+    float* fold = ws_floats(workspace, w.fold);
+    float* ldc = ws_floats(workspace, w.ldc);
+    float* images = ws_floats(workspace, w.images);
+    switch (k.family) {
+        case FLOW_REFUSED: return k.rc;
+        case FLOW_FUSED2:  // f16_tile2.h, FWD
+            return launch_flow_fused2(omega, z_out, sum_log_det, nullptr, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean,
+                                      bn_alpha, interval_consts, nullptr, st, 1, log_q);
+        case FLOW_FUSED_F16:
+            return launch_flow_fused_f16(omega, nullptr, nullptr, nullptr, z_out, sum_log_det, nullptr, M_z, M_p, N, D, S, L,
+                                         U, 0, k.variant, st, params, pstride, bn_mean, bn_alpha, interval_consts);
+        case FLOW_RANGE2_CHAIN:
+            // default per-layer chain of the sampling direction: the whole-flow kernel's tile code, ONE coupling layer per
+            // launch, staged 1-KB loads, half-row stores, prepared prologues (flow_range2_kernel<.., FWD>, flow_fused2.hip)
+            return launch_flow_chain2_fwd(omega, z_out, sum_log_det, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean,
+                                          bn_alpha, nullptr, st, images);
+        default: break;
+    }
     const bool narrow = mfma_supported(D, L, U);
-    const int64_t img_floats = narrow ? mfma_image_floats(D, L) : wide_image_floats(D, L, U);
-    const bool f16 = use_fused && g_flow_variant >= 10;
-    if (interval_consts && !f16)
-        return fail(TNF_EUNSUPPORTED, "tnf_flow_forward_f32: a fused support layer needs the whole-flow kernel");
-    if (f16 && (g_flow_variant == 10 || g_flow_variant == 20) && flow_fused2_supported(D, S, L, U))  // f16_tile2.h, FWD
-        return launch_flow_fused2(omega, z_out, sum_log_det, nullptr, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha,
-                                  interval_consts, nullptr, st, 1, log_q);
-    if (log_q)
-        return fail(TNF_EUNSUPPORTED, "tnf_flow_forward_logq_f32: only the default whole-flow kernel writes log_q "
-                                      "(D=%d S=%d L=%d U=%d, fusion %d)", D, S, L, U, fusion);
-    if (f16)
-        return launch_flow_fused_f16(omega, nullptr, nullptr, nullptr, z_out, sum_log_det, nullptr, M_z, M_p, N, D, S, L,
-                                     U, 0, g_flow_variant, st, params, pstride, bn_mean, bn_alpha, interval_consts);
-    if (!use_fused && narrow && g_layer_variant >= 10 && flow_range2_supported(D, L, U, 1))
-        // default per-layer chain of the sampling direction: the whole-flow kernel's tile code, ONE coupling layer per
-        // launch, staged 1-KB loads, half-row stores, prepared prologues (flow_range2_kernel<.., FWD>, flow_fused2.hip)
-        return launch_flow_chain2_fwd(omega, z_out, sum_log_det, M_z, M_p, N, D, S, L, U, params, pstride, bn_mean, bn_alpha,
-                                      nullptr, st, images);
     rc = launch_flow_prep(params, bn_mean, bn_alpha, fold, ldc, narrow ? images : nullptr, M_p, D, S, L, U, pstride, 0, st);
     if (rc) return rc;
     if (!narrow) {
         rc = launch_wide_images(params, images, M_p, D, S, L, U, pstride, st);
         if (rc) return rc;
     }
-    if (use_fused)
+    if (k.family == FLOW_FP32_WHOLE)
         return launch_flow_fused(omega, images, fold, ldc, z_out, sum_log_det, nullptr, M_z, M_p, N,
                                  D, S, L, U, 0, st);
     const FlowLayout fl = flow_layout(D, S, L, U);
+    const int64_t img_floats = narrow ? mfma_image_floats(D, L) : wide_image_floats(D, L, U);
     const int nl = 2 * S;
     for (int c = 0; c < nl; ++c) {
-        MfmaLayerArgs a;
-        memset(&a, 0, sizeof(a));
+        const FlowLayerAt at = flow_layer_at(fl, c, S, D, images, img_floats);
+        MfmaLayerArgs a = {};
         const bool first = (c == 0), last = (c == nl - 1);
+        set_flow_layer(a, at, params, pstride, U);
         a.z = first ? omega : z_out;
         a.z_out = z_out;
-        a.params = params + (c >> 1) * fl.stage + ((c & 1) ? fl.p_up : 0);
-        a.pstride = pstride;
-        a.image = images + (int64_t)c * img_floats;
-        a.image_stride = (int64_t)nl * img_floats;
-        a.post = fold + (int64_t)c * 2 * D;
-        a.fold_stride = (int64_t)nl * 2 * D;
+        a.post = fold + at.fold_off;
+        a.fold_stride = at.fold_stride;
         a.ld_in = first ? nullptr : sum_log_det;
         a.ld_out = sum_log_det;
         a.ld_sign = 1.f;
         a.ldc = ldc;
         a.add_ldc = last ? 1 : 0;
         a.Mz = first ? M_z : M; a.Mp = M_p; a.N = N;
-        a.D = D; a.L = L; a.U = U; a.upper = (c & 1) ? 0 : 1; a.inverse = 0;
+        a.D = D; a.L = L; a.inverse = 0;
         rc = narrow ? launch_coupling_mfma(a, st) : launch_coupling_wide(a, st);
         if (rc) return rc;
     }
@@ -1542,15 +1538,11 @@ static int flow_padded_checks(const char* fn, const float* z, const float* param
     if (rc) return rc;
     if (S < 1 || L < 1 || U < 1) return fail(TNF_EINVAL, "%s: S=%d L=%d U=%d", fn, S, L, U);
     if (!z || !params || !bn_mean || !bn_alpha) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (pstride < flow_layout(D, S, L, U).total)
-        return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride,
-                    (long long)flow_layout(D, S, L, U).total);
+    rc = check_flow_row(fn, pstride, D, S, L, U);
+    if (rc) return rc;
     if (!flow_padded_supported(D, S, L, U))
         return fail(TNF_EUNSUPPORTED, "%s: no padded whole-flow kernel for D=%d S=%d L=%d U=%d", fn, D, S, L, U);
-    const int64_t need = tnf_flow_padded_workspace_bytes(M_z > M_p ? M_z : M_p, N, D, S, L, U);
-    if (!ws || ws_bytes < need)
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes, (long long)need);
-    return TNF_OK;
+    return check_workspace(fn, ws, ws_bytes, tnf_flow_padded_workspace_bytes(M_z > M_p ? M_z : M_p, N, D, S, L, U));
 }
 
 static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }

@@ -4,6 +4,7 @@
 // of a log_prob chain, the base Gaussian density.  HBM traffic per sample and launch:
 // read D floats + write D floats (+ 8 B of running log-det), i.e. 520 B at D = 64.
 #include <cstring>
+#include "flow_layer.h"
 #include "mfma_tile.h"
 #include "tnf_common.h"
 
@@ -609,24 +610,20 @@ int flow_forward_batch_layer(int c, const float* z_in, const float* params, floa
                              void* ws, hipStream_t st) {
     const FbWs w = fb_ws(ws, Mp, D);
     const FlowLayout fl = flow_layout(D, S, L, U);
-    const int nl = 2 * S;
     const int64_t img_floats = mfma_image_floats(D, L);
     if (!moments) moments = w.moments;
     if (N > 0) {
         MfmaLayerArgs a = {};
+        set_flow_layer(a, flow_layer_at(fl, c, S, D, w.images, img_floats), params, pstride, U);
         a.z = z_in;
         a.z_out = z_out;
-        a.params = params + (c >> 1) * fl.stage + ((c & 1) ? fl.p_up : 0);
-        a.pstride = pstride;
-        a.image = w.images + (int64_t)c * img_floats;
-        a.image_stride = (int64_t)nl * img_floats;
         a.pre = c == 0 ? nullptr : w.fold;
         a.fold_stride = 2 * (int64_t)D;
         a.ld_in = c == 0 ? nullptr : sum_log_det;
         a.ld_out = sum_log_det;
         a.ld_sign = 1.f;
         a.Mz = M; a.Mp = Mp; a.N = N;
-        a.D = D; a.L = L; a.U = U; a.upper = (c & 1) ? 0 : 1; a.inverse = 0;
+        a.D = D; a.L = L; a.inverse = 0;
         int rc = launch_coupling_mfma(a, st);
         if (rc) return rc;
     }
@@ -840,19 +837,16 @@ int launch_flow_forward_train_fwd(const float* omega, const float* params, float
     if (rc) return rc;
     for (int c = 0; c < nl; ++c) {
         MfmaLayerArgs a = {};
+        set_flow_layer(a, flow_layer_at(fl, c, S, D, images, img_floats), params, pstride, U);
         a.z = c == 0 ? omega : states + (int64_t)(c - 1) * plane;
         a.z_out = states + (int64_t)c * plane;
-        a.params = params + (c >> 1) * fl.stage + ((c & 1) ? fl.p_up : 0);
-        a.pstride = pstride;
-        a.image = images + (int64_t)c * img_floats;
-        a.image_stride = (int64_t)nl * img_floats;
         a.pre = c == 0 ? nullptr : folds + (int64_t)(c - 1) * Mp * 2 * D;
         a.fold_stride = 2 * (int64_t)D;
         a.ld_in = c == 0 ? nullptr : sum_log_det;
         a.ld_out = sum_log_det;
         a.ld_sign = 1.f;
         a.Mz = M; a.Mp = Mp; a.N = N;
-        a.D = D; a.L = L; a.U = U; a.upper = (c & 1) ? 0 : 1; a.inverse = 0;
+        a.D = D; a.L = L; a.inverse = 0;
         rc = launch_coupling_mfma(a, st);
         if (rc) return rc;
         rc = launch_bn_moments(states + (int64_t)c * plane, sums, M * N, D, st);
@@ -929,21 +923,17 @@ int launch_flow_forward_train_bwd(const float* omega, const float* params, const
             cur ^= 1;
         }
         // coupling layer c (PQ was zeroed by fold_backward_ctx_kernel when it consumed it)
-        BwdArgs a;
-        memset(&a, 0, sizeof(a));
-        const int64_t poff = (c >> 1) * fl.stage + ((c & 1) ? fl.p_up : 0);
+        const FlowLayerAt at = flow_layer_at(fl, c, S, D, images, img_floats);
+        BwdArgs a = {};
+        set_flow_layer(a, at, params, pstride, U);
         a.z = c == 0 ? omega : states + (int64_t)(c - 1) * plane;
-        a.params = params + poff;
         a.g_zout = gbuf[cur];
         a.g_ld = g_sld;
         a.ld_scale = 1.f;
         a.g_z = (c == 0 && g_omega) ? g_omega : gbuf[cur ^ 1];
-        a.g_params = g_params + poff;
+        a.g_params = g_params + at.poff;
+        a.gpstride = gpstride;
         a.M = M; a.Mp = Mp; a.N = N;
-        a.pstride = pstride; a.gpstride = gpstride;
-        a.U = U; a.upper = (c & 1) ? 0 : 1;
-        a.image = images + (int64_t)c * img_floats;
-        a.image_stride = (int64_t)nl * img_floats;
         a.fold = c == 0 ? nullptr : folds + (int64_t)(c - 1) * Mp * 2 * D;
         a.g_fold = c == 0 ? nullptr : PQ;
         a.fold_stride = 2 * (int64_t)D;
