@@ -9,19 +9,6 @@
 
 namespace tnf {
 
-template <typename T>
-__device__ __forceinline__ T bw_tanh(T x);
-template <>
-__device__ __forceinline__ float bw_tanh<float>(float x) { return tanhf(x); }
-template <>
-__device__ __forceinline__ double bw_tanh<double>(double x) { return tanh(x); }
-template <typename T>
-__device__ __forceinline__ T bw_exp(T x);
-template <>
-__device__ __forceinline__ float bw_exp<float>(float x) { return expf(x); }
-template <>
-__device__ __forceinline__ double bw_exp<double>(double x) { return exp(x); }
-
 // ---------------------------------------------------------------------------
 // RealNVP.  Forward (bijectors.py:168-179 / 194-205):
 //   t, s = MLP_t(x), MLP_s(x);  fwd: y' = t + y e^s;  inv: y' = (y - t) e^-s;  ld = sum(s)
@@ -107,8 +94,8 @@ coupling_backward_kernel(const T* __restrict__ z, const T* __restrict__ params,
                 a_t += bt[o];
                 a_s += bs[o];
                 if (l < L) {
-                    a_t = bw_tanh<T>(a_t);
-                    a_s = bw_tanh<T>(a_s);
+                    a_t = Mth<T>::tanh(a_t);
+                    a_s = Mth<T>::tanh(a_s);
                 }
                 ot[i * W + o] = a_t;
                 os[i * W + o] = a_s;
@@ -129,12 +116,12 @@ coupling_backward_kernel(const T* __restrict__ z, const T* __restrict__ params,
         const T gl = g_ld[m * N + n0 + i];
         T dy, dt, dsv;
         if (inverse) {
-            const T em = bw_exp<T>(-s);
+            const T em = Mth<T>::exp(-s);
             dy = gy * em;
             dt = -dy;
             dsv = -gy * ((y - t) * em) + gl;
         } else {
-            const T e = bw_exp<T>(s);
+            const T e = Mth<T>::exp(s);
             dy = gy * e;
             dt = gy;
             dsv = gy * y * e + gl;
@@ -367,7 +354,7 @@ affine_backward_kernel(const T* __restrict__ z, const T* __restrict__ params,
         double sa = 0.0, sb = 0.0;
         if (r < rpi) {
             const T a = p[dc + d], b = p[D + dc + d];
-            const T e = bw_exp<T>(inverse ? -a : a);
+            const T e = Mth<T>::exp(inverse ? -a : a);
             for (int64_t row = r0 + r; row < r1; row += rpi) {
                 const int64_t at = (m * N + row) * D + dc + d;
                 const T g = g_zout[at], zv = z[at];

@@ -39,7 +39,7 @@ cond_absmax_kernel(const float* __restrict__ W, const float* __restrict__ b, int
     }
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < P; i += (int64_t)gridDim.x * 256)
         mx = fmaxf(mx, fabsf(b[i]));
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) atomicMax(maxbits, __float_as_uint(mx));  // non-negative floats order like uints
 }
 
@@ -72,7 +72,7 @@ cond_image_kernel(const float* __restrict__ W, const float* __restrict__ b, int6
             v0 *= sc;
             v1 *= sc;
             h8 hi, lo;
-            csplit8(v0, v1, hi, lo);
+            split8(v0, v1, hi, lo);
             tp[(ks * 2 + 0) * 64 + lane] = __builtin_bit_cast(u4, hi);
             tp[(ks * 2 + 1) * 64 + lane] = __builtin_bit_cast(u4, lo);
         }
@@ -139,7 +139,7 @@ cond_flow_kernel(CondArgs a) {
         const float* hr = a.h + m * a.ldh;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-            csplit8(*reinterpret_cast<const f4*>(hr + 32 * ks + 8 * q),
+            split8(*reinterpret_cast<const f4*>(hr + 32 * ks + 8 * q),
                     *reinterpret_cast<const f4*>(hr + 32 * ks + 8 * q + 4), bh[bt][ks], bl[bt][ks]);
     }
     const float inv = *a.inv_scale;

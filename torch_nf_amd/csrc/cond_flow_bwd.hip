@@ -51,7 +51,7 @@ cond_timage_kernel(const float* __restrict__ W, int64_t ldw, CondCfg cfg, const 
                 v[e] = ok ? w * scale : 0.f;
             }
             h8 hi, lo;
-            csplit8((f4){v[0], v[1], v[2], v[3]}, (f4){v[4], v[5], v[6], v[7]}, hi, lo);
+            split8((f4){v[0], v[1], v[2], v[3]}, (f4){v[4], v[5], v[6], v[7]}, hi, lo);
             tp[(jt * 2 + 0) * 64 + lane] = __builtin_bit_cast(u4, hi);
             tp[(jt * 2 + 1) * 64 + lane] = __builtin_bit_cast(u4, lo);
         }
@@ -144,7 +144,7 @@ cond_flow_bwd_kernel(CondBwdArgs a) {
         const float* hr = a.h + mrow[bt] * a.ldh;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-            csplit8(*reinterpret_cast<const f4*>(hr + 32 * ks + 8 * q),
+            split8(*reinterpret_cast<const f4*>(hr + 32 * ks + 8 * q),
                     *reinterpret_cast<const f4*>(hr + 32 * ks + 8 * q + 4), bh[bt][ks], bl[bt][ks]);
     }
     {   // g_z0 = -g_lp * z0; z0 = [x1 | x2_out] of the coupling layer computed last (slot 2(S-1)+1, upper)
@@ -180,7 +180,7 @@ cond_flow_bwd_kernel(CondBwdArgs a) {
 #pragma unroll
         for (int bt = 0; bt < BT; ++bt) {
             const float x = xsel[bt];
-            csplit8((f4){x * d8[bt][0], x * d8[bt][1], x * d8[bt][2], x * d8[bt][3]},
+            split8((f4){x * d8[bt][0], x * d8[bt][1], x * d8[bt][2], x * d8[bt][3]},
                     (f4){x * d8[bt][4], x * d8[bt][5], x * d8[bt][6], x * d8[bt][7]}, Bh[bt], Bl[bt]);
         }
 #pragma unroll
@@ -188,11 +188,11 @@ cond_flow_bwd_kernel(CondBwdArgs a) {
             const h8 ah = __builtin_bit_cast(h8, tp[(jt * 2 + 0) * 64 + lane]);
             const h8 al = __builtin_bit_cast(h8, tp[(jt * 2 + 1) * 64 + lane]);
 #pragma unroll
-            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = cmfma32h(ah, Bh[bt], gacc[bt][jt]);
+            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = mfma32h(ah, Bh[bt], gacc[bt][jt]);
 #pragma unroll
-            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = cmfma32h(al, Bh[bt], gacc[bt][jt]);
+            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = mfma32h(al, Bh[bt], gacc[bt][jt]);
 #pragma unroll
-            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = cmfma32h(ah, Bl[bt], gacc[bt][jt]);
+            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = mfma32h(ah, Bl[bt], gacc[bt][jt]);
         }
     };
     float ones[BT];
@@ -485,7 +485,7 @@ cond_gh_kernel(CondBwdArgs a) {
 #pragma unroll
         for (int bt = 0; bt < BT; ++bt) {
             const float x = xsel[bt];
-            csplit8((f4){x * d8[bt][0], x * d8[bt][1], x * d8[bt][2], x * d8[bt][3]},
+            split8((f4){x * d8[bt][0], x * d8[bt][1], x * d8[bt][2], x * d8[bt][3]},
                     (f4){x * d8[bt][4], x * d8[bt][5], x * d8[bt][6], x * d8[bt][7]}, Bh[bt], Bl[bt]);
         }
 #pragma unroll
@@ -493,11 +493,11 @@ cond_gh_kernel(CondBwdArgs a) {
             const h8 ah = __builtin_bit_cast(h8, tp[(jt * 2 + 0) * 64 + lane]);
             const h8 al = __builtin_bit_cast(h8, tp[(jt * 2 + 1) * 64 + lane]);
 #pragma unroll
-            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = cmfma32h(ah, Bh[bt], gacc[bt][jt]);
+            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = mfma32h(ah, Bh[bt], gacc[bt][jt]);
 #pragma unroll
-            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = cmfma32h(al, Bh[bt], gacc[bt][jt]);
+            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = mfma32h(al, Bh[bt], gacc[bt][jt]);
 #pragma unroll
-            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = cmfma32h(ah, Bl[bt], gacc[bt][jt]);
+            for (int bt = 0; bt < BT; ++bt) gacc[bt][jt] = mfma32h(ah, Bl[bt], gacc[bt][jt]);
         }
     };
     float ones[BT];
@@ -615,7 +615,7 @@ cond_gh_kernel(CondBwdArgs a) {
 __global__ void __launch_bounds__(256) cond_gmax_kernel(const float* __restrict__ g, int64_t n, unsigned* __restrict__ maxbits) {
     float mx = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) mx = fmaxf(mx, fabsf(g[i]));
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) atomicMax(maxbits, __float_as_uint(mx));
 }
 
@@ -752,7 +752,7 @@ cond_hsplit_kernel(const float* __restrict__ h, int64_t ldh, int64_t M, u4* __re
             v[e] = m < M ? x : 0.f;
         }
         h8 hi, lo;
-        csplit8((f4){v[0], v[1], v[2], v[3]}, (f4){v[4], v[5], v[6], v[7]}, hi, lo);
+        split8((f4){v[0], v[1], v[2], v[3]}, (f4){v[4], v[5], v[6], v[7]}, hi, lo);
         himg[((g * JT + jt) * 2 + 0) * 64 + lane] = __builtin_bit_cast(u4, hi);
         himg[((g * JT + jt) * 2 + 1) * 64 + lane] = __builtin_bit_cast(u4, lo);
     }
@@ -980,7 +980,7 @@ cond_gw_kernel(GwArgs a) {
 #if TNF_COND_ABLATE == 4  // timing experiment: no operand split
                     ah = al = __builtin_bit_cast(h8, (u4){__float_as_uint(a0[0]), __float_as_uint(a0[1]), __float_as_uint(a1[0]), __float_as_uint(a1[1])});
 #else
-                    csplit8(a0, a1, ah, al);
+                    split8(a0, a1, ah, al);
 #endif
 #endif
 #if TNF_GW_ABL == 1  // timing experiment: no MFMAs
@@ -993,9 +993,9 @@ cond_gw_kernel(GwArgs a) {
 #else
 #pragma unroll
                     for (int jt = 0; jt < JT; ++jt) {
-                        acc[i][jt] = cmfma32h(ah, Bh[jt], acc[i][jt]);
-                        acc[i][jt] = cmfma32h(al, Bh[jt], acc[i][jt]);
-                        acc[i][jt] = cmfma32h(ah, Bl[jt], acc[i][jt]);
+                        acc[i][jt] = mfma32h(ah, Bh[jt], acc[i][jt]);
+                        acc[i][jt] = mfma32h(al, Bh[jt], acc[i][jt]);
+                        acc[i][jt] = mfma32h(ah, Bl[jt], acc[i][jt]);
                     }
 #endif
                 }

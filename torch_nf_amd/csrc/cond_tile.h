@@ -1,5 +1,5 @@
 // Shared pieces of the conditional-flow kernels (cond_flow.hip: forward, cond_flow_bwd.hip: backward):
-// split-f16 helpers, the tile program, the LDS tile stream and the per-tile MFMA.
+// the tile program, the LDS tile stream and the per-tile MFMA (split-f16 helpers: wave_prims.h, round toward zero).
 #pragma once
 #ifndef TNF_COND_ABLATE
 #define TNF_COND_ABLATE 0
@@ -8,33 +8,6 @@
 #include "tnf_common.h"
 
 namespace tnf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 cmfma32h(h8 a, h8 b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-// v = hi + lo, hi = rtz_f16(v), lo = rtz_f16(v - hi)   (pairs packed into one dword each)
-__device__ __forceinline__ void csplit2(float v0, float v1, unsigned& hi, unsigned& lo) {
-    const auto h = __builtin_amdgcn_cvt_pkrtz(v0, v1);
-    const unsigned hb = __builtin_bit_cast(unsigned, h);
-    // in place ("+v"), never into a fresh register: the inline-asm rule of f16_tile.h
-    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(hb));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(hb));
-    hi = hb;
-    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v0, v1));
-}
-__device__ __forceinline__ void csplit8(f4 v0, f4 v1, h8& hi, h8& lo) {
-    unsigned a0, a1, a2, a3, b0, b1, b2, b3;
-    csplit2(v0[0], v0[1], a0, b0);
-    csplit2(v0[2], v0[3], a1, b1);
-    csplit2(v1[0], v1[1], a2, b2);
-    csplit2(v1[2], v1[3], a3, b3);
-    hi = __builtin_bit_cast(h8, (u4){a0, a1, a2, a3});
-    lo = __builtin_bit_cast(h8, (u4){b0, b1, b2, b3});
-}
 
 // ---------------------------------------------------------------------------
 // The tile program: which 16 parameter-row entries tile t holds, in consumption order.
@@ -167,8 +140,6 @@ __device__ __forceinline__ float cond_scale(unsigned maxbits) {
 // in flight: the image streams from L2 / Infinity Cache with ~2 us latency under load, several chunks of
 // MFMA work.  The wait before the barrier is a COUNTED vmcnt (the NS-2 newer copies stay in flight; a
 // plain __syncthreads() would drain them with vmcnt(0)) followed by a raw s_barrier.
-typedef __attribute__((address_space(3))) void lds_void;
-
 template <int TILE_U4_, int G, int NW, int NS>
 struct TileStream {
     static constexpr int TILE_U4 = TILE_U4_;
@@ -225,12 +196,6 @@ struct TileStream {
     }
 };
 
-// fast transcendental forms (v_exp_f32 / v_rcp_f32 / v_log_f32, ~1 ulp): the precise library versions
-// cost ~50 VALU instructions each and, with two waves per SIMD, that is time the matrix pipe idles
-__device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * sig2(kTwoLog2e * x); }
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(kLog2e * x); }
-__device__ __forceinline__ float fast_log(float x) { return kLn2 * __builtin_amdgcn_logf(x); }
-
 // MFMA A operands of one tile (split-f16 halves per K step) + the accumulator's initial value
 template <int KS>
 struct TileOps {
@@ -256,12 +221,12 @@ __device__ __forceinline__ void gemm_ops(const TileOps<KS>& o, const h8 (&bh)[BT
         const h8 ah = __builtin_bit_cast(h8, o.a[ks][0]);
         const h8 al = __builtin_bit_cast(h8, o.a[ks][1]);
 #pragma unroll
-        for (int bt = 0; bt < BT; ++bt) P[bt] = cmfma32h(ah, bh[bt][ks], P[bt]);
+        for (int bt = 0; bt < BT; ++bt) P[bt] = mfma32h(ah, bh[bt][ks], P[bt]);
 #if TNF_COND_ABLATE != 1  // timing experiment 1: one MFMA per K step instead of three
 #pragma unroll
-        for (int bt = 0; bt < BT; ++bt) P[bt] = cmfma32h(ah, bl[bt][ks], P[bt]);
+        for (int bt = 0; bt < BT; ++bt) P[bt] = mfma32h(ah, bl[bt][ks], P[bt]);
 #pragma unroll
-        for (int bt = 0; bt < BT; ++bt) P[bt] = cmfma32h(al, bh[bt][ks], P[bt]);
+        for (int bt = 0; bt < BT; ++bt) P[bt] = mfma32h(al, bh[bt][ks], P[bt]);
 #endif
     }
 }

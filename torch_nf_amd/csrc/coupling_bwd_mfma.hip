@@ -98,18 +98,6 @@ __device__ __forceinline__ void build_bwd_image(float* img, const float* __restr
 
 __device__ __forceinline__ void lds_plus(float* p, float v) { *p += v; }
 
-// acc layout (lane (s,q), reg j = row 4q+j, col s)  ->  operand layout with K = samples
-// (lane (c = lane&15, kq = lane>>4), reg i = element [row c][sample 4i + kq]).
-__device__ __forceinline__ f4 transpose_tile(f4 v, float* scr, int lane) {
-    const int s = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) scr[(4 * q + j) * 17 + s] = v[j];
-    f4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = scr[s * 17 + 4 * i + q];
-    return o;
-}
-
 // D[rows][cols] += A[rows][K = 16 samples] . B[K][cols]   (both operands already transposed)
 __device__ __forceinline__ f4 outer16(f4 a_t, f4 b_t, f4 acc) {
 #pragma unroll
@@ -405,13 +393,6 @@ coupling_bwd_mfma_kernel(BwdArgs a) {
     for (int turn = 0; turn < 4; ++turn) {
         if (wave == turn) {
             const int c = lane & 15;  // column of the dW accumulators; rows are 4q + j
-            auto red16 = [&](float v) -> float {  // sum over the 16 sample lanes of a q-group
-                v += __shfl_xor(v, 1);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 4);
-                v += __shfl_xor(v, 8);
-                return v;
-            };
             float* gp = gacc;
             {   // layer 0
                 float* gwt = gp;
@@ -429,7 +410,7 @@ coupling_bwd_mfma_kernel(BwdArgs a) {
                             lds_plus(gws + f * U + u, dW0[1][mm][j]);
                         }
                     }
-                    const float bt = red16(db0[0][j]), bs = red16(db0[1][j]);
+                    const float bt = row16_sum(db0[0][j]), bs = row16_sum(db0[1][j]);
                     if (s == 0 && u < U) {
                         lds_plus(gbt + u, bt);
                         lds_plus(gbs + u, bs);
@@ -450,7 +431,7 @@ coupling_bwd_mfma_kernel(BwdArgs a) {
                         lds_plus(gwt + ki * U + ko, dWh[l][0][j]);
                         lds_plus(gws + ki * U + ko, dWh[l][1][j]);
                     }
-                    const float bt = red16(dbh[l][0][j]), bs = red16(dbh[l][1][j]);
+                    const float bt = row16_sum(dbh[l][0][j]), bs = row16_sum(dbh[l][1][j]);
                     if (s == 0 && ko < U) {
                         lds_plus(gbt + ko, bt);
                         lds_plus(gbs + ko, bs);
@@ -472,7 +453,7 @@ coupling_bwd_mfma_kernel(BwdArgs a) {
                             lds_plus(gwt + k * H + o, dW2[0][mo][j]);
                             lds_plus(gws + k * H + o, dW2[1][mo][j]);
                         }
-                        const float bt = red16(db2[0][mo][j]), bs = red16(db2[1][mo][j]);
+                        const float bt = row16_sum(db2[0][mo][j]), bs = row16_sum(db2[1][mo][j]);
                         if (s == 0 && o < H) {
                             lds_plus(gbt + o, bt);
                             lds_plus(gbs + o, bs);
@@ -480,7 +461,7 @@ coupling_bwd_mfma_kernel(BwdArgs a) {
                     }
             }
             if (finalize && a.glp_sum) {
-                const float tot = red16(glp_acc);
+                const float tot = row16_sum(glp_acc);
                 if (lane == 0) atomicAdd(a.glp_sum + mp, tot);
             }
             if (a.g_fold) {  // fold-constant gradients: reduce over the 16 sample lanes, then LDS
@@ -489,8 +470,8 @@ coupling_bwd_mfma_kernel(BwdArgs a) {
                 for (int mm = 0; mm < HT; ++mm)
         #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float ax = red16(dAx[mm][j]), bx = red16(dBx[mm][j]);
-                        const float ay = red16(dAy[mm][j]), by = red16(dBy[mm][j]);
+                        const float ax = row16_sum(dAx[mm][j]), bx = row16_sum(dBx[mm][j]);
+                        const float ay = row16_sum(dAy[mm][j]), by = row16_sum(dBy[mm][j]);
                         if (s == 0) {
                             const int fx = c_off + 16 * mm + 4 * q + j, fy = t_off + 16 * mm + 4 * q + j;
                             lds_plus(gf + fx, ax);

@@ -731,7 +731,7 @@ fold_sums_kernel(const float* __restrict__ g, const float* __restrict__ v, const
         __syncthreads();
         float sacc = 0.f;
         for (int64_t row = r0 + tid; row < r1; row += 256) sacc += g_sld[m * N + row];
-        for (int off = 32; off > 0; off >>= 1) sacc += __shfl_xor(sacc, off);
+        sacc = wave_sum(sacc);
         if ((tid & 63) == 0) atomicAdd(Ssum + mp, sacc);
     }
 }

@@ -420,8 +420,7 @@ wide_gw_kernel(WideGwArgs a) {
     }
     if (maf) return;
     // bias: row sum of the delta block -- this lane holds samples 4q .. 4q+3 of row c
-    bsum += __shfl_xor(bsum, 16);
-    bsum += __shfl_xor(bsum, 32);
+    bsum = reduce_q(bsum);
     if (q == 0 && 16 * ta + c < dout) part[bbase + 16 * ta + c] = bsum;
 }
 

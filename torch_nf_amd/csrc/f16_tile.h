@@ -1,64 +1,13 @@
-// Split-f16 operand helpers shared by the whole-flow kernels (flow_fused_f16.hip, flow_bwd_f16.hip):
-// v = hi + lo with hi = rtz_f16(v), lo = rtz_f16(v - hi); an fp32-accurate contraction is three f16
-// MFMAs (hi.hi + lo.hi + hi.lo) with fp32 accumulate.  See flow_fused_f16.hip for the measurements.
+// Split-f16 operand image of one coupling layer, shared by the whole-flow kernels (flow_fused_f16.hip,
+// flow_bwd_f16.hip).  The split itself (round toward zero here) is wave_prims.h's; see flow_fused_f16.hip for the
+// measurements.
 #pragma once
+#if defined(TNF_ABLATE) && TNF_ABLATE == 2  // timing experiment only: split without remainder (scope: wave_prims.h)
+#define TNF_SPLIT_RTZ_NO_REMAINDER 1
+#endif
 #include "mfma_tile.h"
 
 namespace tnf {
-
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
-// Inline-asm rule of this code base (measured the hard way, flow_fused2.hip round 2): hipcc neither sees the registers
-// an asm VALU instruction READS as results of an in-flight MFMA, nor pads the WAR / WAW hazards of the registers it
-// WRITES against MFMAs still reading (SrcC, up to 7 wait states for an 8-pass MFMA) or writing them.  A fresh "=v"
-// output may land in exactly such a register -- results then change with the schedule and from run to run.  So an asm
-// VALU instruction here only ever (a) reads results of ordinary VALU instructions and (b) writes IN PLACE ("+v") over a
-// value an ordinary VALU instruction produced after the MFMAs in question: the compiler resolved every MFMA hazard of
-// that register when it scheduled the producer, and it copies the value first (v_mov, visible) if it is still live.
-// two floats -> packed (hi, hi) and (lo, lo) f16 pairs
-struct HiLo {
-    unsigned hi, lo;
-};
-__device__ __forceinline__ HiLo split2v(float v0, float v1) {
-    const auto h = __builtin_amdgcn_cvt_pkrtz(v0, v1);
-#if TNF_ABLATE == 2  // timing experiment only: no remainder
-    return HiLo{__builtin_bit_cast(unsigned, h), __builtin_bit_cast(unsigned, h)};
-#endif
-    // v - (float)hi as ONE mixed-precision FMA reading the f16 half directly (hipcc does not
-    // select v_fma_mix_f32 for this pattern; it emits v_cvt_f32_f16 + v_sub_f32).  Exact: the
-    // difference of v and its rtz-f16 truncation is representable in fp32.
-    const unsigned hb = __builtin_bit_cast(unsigned, h);
-    // the remainder replaces the value IN PLACE ("+v"): see the inline-asm rule above
-    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(hb));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(hb));
-    const auto l = __builtin_amdgcn_cvt_pkrtz(v0, v1);
-    return HiLo{hb, __builtin_bit_cast(unsigned, l)};
-}
-// (vector elements cannot bind to references, hence the macro)
-#define split2(V0, V1, HI, LO)              \
-    do {                                    \
-        const HiLo hl_ = split2v((V0), (V1)); \
-        (HI) = hl_.hi;                      \
-        (LO) = hl_.lo;                      \
-    } while (0)
-
-__device__ __forceinline__ void split4(f4 v, h4& hi, h4& lo) {
-    u2 a, b;
-    split2(v[0], v[1], a[0], b[0]);
-    split2(v[2], v[3], a[1], b[1]);
-    hi = __builtin_bit_cast(h4, a);
-    lo = __builtin_bit_cast(h4, b);
-}
-
-__device__ __forceinline__ f4 mfma16h(h4 a, h4 b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f4 mfma32h(h8 a, h8 b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 // LDS / global image of one layer's split-f16 operands: 16-byte groups [g][lane], then the
 // fp32 bias groups [g][q][4] exactly as in LdsLayerImage.

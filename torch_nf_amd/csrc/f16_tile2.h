@@ -39,12 +39,15 @@
 //    by r_hi . w_lo as a K = 16 product, was 3.5 % faster and wrong for that reason.)  Every accumulation chain here
 //    stays within ONE MFMA shape: K = 32 chains for the first layer at D = 64, K = 16 chains everywhere else.
 #pragma once
-#include "f16_tile.h"
-#include "support_math.h"
-
 #ifndef TNF2_ABL
 #define TNF2_ABL 0
 #endif
+#if TNF2_ABL == 4  // timing experiment only: split without remainder (scope: wave_prims.h)
+#define TNF_SPLIT_RNE_NO_REMAINDER 1
+#endif
+#include "f16_tile.h"
+#include "support_math.h"
+
 // Explicit pipe interleave of the layer body, all measured and none adopted -- DESIGN.md 3.11.2:
 //   1 / 2: __builtin_amdgcn_iglp_opt(0 / 1);  3: one MFMA then five vector instructions, 24 NT times per layer, as
 //   __builtin_amdgcn_sched_group_barrier groups;  4: one MFMA, two transcendentals, three other vector instructions.
@@ -54,21 +57,7 @@
 
 namespace tnf {
 
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-// hi = rne_f16(v), lo = rne_f16(v - hi) (the remainder is exact in fp32).  |v| >= 65520: hi = +-inf, lo = -+inf.
-__device__ __forceinline__ HiLo split2r(float v0, float v1) {
-    const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{v0, v1}, h2));  // v_cvt_pk_f16_f32
-#if TNF2_ABL == 4  // timing experiment only: no remainder
-    return HiLo{hb, hb};
-#endif
-    // in place ("+v"), never into a fresh register: the inline-asm rule of f16_tile.h
-    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(hb));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(hb));
-    const unsigned lb = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{v0, v1}, h2));
-    return HiLo{hb, lb};
-}
+// (operands are split with wave_prims.h's round-to-nearest split2r / split4r: point 3 above)
 
 // ---- reduced-precision experiment (BASELINE configs[4], "fp32 vs bf16 tolerance sweep"): PREC = 1 evaluates every
 // contraction as ONE bf16 MFMA (operands rounded to bf16 once, fp32 accumulate) instead of the three split-f16
@@ -84,13 +73,6 @@ __device__ __forceinline__ f4 mfma16b(u2 a, u2 b, f4 c) {
 }
 __device__ __forceinline__ f4 mfma32b(u4 a, u4 b, f4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
-}
-
-// four values -> hi(4), lo(4)
-__device__ __forceinline__ void split4r(f4 v, h4& hi, h4& lo) {
-    const HiLo a = split2r(v[0], v[1]), b = split2r(v[2], v[3]);
-    hi = __builtin_bit_cast(h4, u2{a.hi, b.hi});
-    lo = __builtin_bit_cast(h4, u2{a.lo, b.lo});
 }
 
 // one K = 16 contraction  c + w . r  on split operands: w_hi.r_hi + w_hi.r_lo + w_lo.r_hi, one MFMA shape throughout
@@ -110,21 +92,6 @@ __device__ __forceinline__ float sig2s(float a, float S) {
 __device__ __forceinline__ f4 sig2s_4(f4 v, float S) {
     return f4{sig2s(v[0], S), sig2s(v[1], S), sig2s(v[2], S), sig2s(v[3], S)};
 }
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-// exponent kappa with mx * 2^kappa in [1, 2), clamped; 0 for mx = 0 / non-finite
-__device__ __forceinline__ int norm_exponent(float mx, int lo, int hi) {
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 0;
-    int e;
-    (void)__builtin_frexpf(mx, &e);  // mx = m 2^e, m in [0.5, 1)
-    int k = 1 - e;
-    return k < lo ? lo : (k > hi ? hi : k);
-}
-__device__ __forceinline__ float pow2i(int k) { return __builtin_ldexpf(1.f, k); }
 
 // LDS image of one coupling layer (4-byte units)
 template <int H, int L>
@@ -171,7 +138,7 @@ __device__ __forceinline__ int layer_kappa(const float* __restrict__ p, int U, i
             mx = fmaxf(mx, fabsf(kTwoLog2e * ld_sel(ws, f * U + r, ok) * a));
         }
     (void)D;
-    return norm_exponent(wave_max(mx), -30, 30);
+    return pow2_norm(wave_max(mx), -30, 30);
 }
 
 // K = 16 weight group: four fp32 values -> [hi(4) | lo(4)]  (PREC = 1: [bf16(4) | 0])
@@ -230,7 +197,7 @@ __device__ __forceinline__ void build_image2(float* img, const float* __restrict
             float mx = 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) mx = fmaxf(mx, fabsf(w.wh[l][net][j]));
-            const float S = pow2i(norm_exponent(wave_max(mx), -15, 40));
+            const float S = pow2i(pow2_norm(wave_max(mx), -15, 40));
             Sst[l][net] = S;
 #pragma unroll
             for (int j = 0; j < 4; ++j) w.wh[l][net][j] *= S;
@@ -260,7 +227,7 @@ __device__ __forceinline__ void build_image2(float* img, const float* __restrict
                 if (net == 0) w.w2[0][mo][j] *= sig_next;
                 mx = fmaxf(mx, fabsf(w.w2[net][mo][j]));
             }
-        const float S = pow2i(norm_exponent(wave_max(mx), -15, 40));
+        const float S = pow2i(pow2_norm(wave_max(mx), -15, 40));
         Sst[L - 1][net] = S;
 #pragma unroll
         for (int mo = 0; mo < HT; ++mo)

@@ -134,8 +134,8 @@ __device__ __forceinline__ void build_image3(float* img, const float* __restrict
             mx = fmaxf(mx, fabsf(v[e]));
         }
         cs += __shfl_xor(cs, 32);
-        const float St = pow2i(norm_exponent(net_max(mx, lane, 0), -15, 40));
-        const float Ss = pow2i(norm_exponent(net_max(mx, lane, 1), -15, 40));
+        const float St = pow2i(pow2_norm(net_max(mx, lane, 0), -15, 40));
+        const float Ss = pow2i(pow2_norm(net_max(mx, lane, 1), -15, 40));
         Sst[l][0] = St;
         Sst[l][1] = Ss;
         const float S = net ? Ss : St;
@@ -174,8 +174,8 @@ __device__ __forceinline__ void build_image3(float* img, const float* __restrict
             }
             ct += __shfl_xor(ct, 32);
             cs += __shfl_xor(cs, 32);
-            const float St = pow2i(norm_exponent(wave_max(mt), -15, 40));
-            const float Ss = pow2i(norm_exponent(wave_max(ms), -15, 40));
+            const float St = pow2i(pow2_norm(wave_max(mt), -15, 40));
+            const float Ss = pow2i(pow2_norm(wave_max(ms), -15, 40));
             Sst[L - 1][0] = St;
             Sst[L - 1][1] = Ss;
 #pragma unroll
@@ -211,8 +211,8 @@ __device__ __forceinline__ void build_image3(float* img, const float* __restrict
                 mx = fmaxf(mx, fabsf(v[e]));
             }
             cs += __shfl_xor(cs, 32);
-            const float St = pow2i(norm_exponent(net_max(mx, lane, 0), -15, 40));
-            const float Ss = pow2i(norm_exponent(net_max(mx, lane, 1), -15, 40));
+            const float St = pow2i(pow2_norm(net_max(mx, lane, 0), -15, 40));
+            const float Ss = pow2i(pow2_norm(net_max(mx, lane, 1), -15, 40));
             Sst[L - 1][0] = St;
             Sst[L - 1][1] = Ss;
             const float S = net ? Ss : St;

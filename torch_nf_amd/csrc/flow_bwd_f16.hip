@@ -187,7 +187,7 @@ flow_gmax_kernel(const float* __restrict__ g, int64_t n, unsigned* __restrict__ 
         for (int u = 0; u < 4; ++u) m = fmaxf(fmaxf(m, fmaxf(fabsf(v[u][0]), fabsf(v[u][1]))), fmaxf(fabsf(v[u][2]), fabsf(v[u][3])));
     }
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) m = fmaxf(m, fabsf(g[i]));
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -720,17 +720,7 @@ flow_bwd_reduce_kernel(const int* __restrict__ partials, const float* __restrict
     const int64_t mp = grid_m();  // parameter rows ride on grid y and z (grid_xm): any Mp
     if (mp >= Mp) return;
     const int64_t prow = (int64_t)nl * (P + 2 * D);
-    float isc = 1.f;
-    {
-        const float gm = __uint_as_float(*gmax);
-        if (gm > 0.f && gm < 3.0e38f) {
-            int e;
-            (void)frexpf(gm, &e);
-            int k = 1 - e;
-            k = k > 120 ? 120 : (k < -120 ? -120 : k);
-            isc = ldexpf(1.f, -k);
-        }
-    }
+    const float isc = pow2_scale(__uint_as_float(*gmax)).isc;
     const float unfx = isc / fx;
     const float poison = *overflow ? __builtin_nanf("") : 0.f;
     const int* src = partials + mp * nred * prow;
@@ -788,6 +778,62 @@ flow_bwd_reduce_kernel(const int* __restrict__ partials, const float* __restrict
     }
 }
 
+// ---- pieces shared by the two whole-flow backward kernels (flow_bwd_f16_kernel here, flow_bwd_pair_kernel) ----------
+// layer image c -> ring slot by LDS-DMA (global_load_lds_dwordx4: 1 KB per wave-instruction, no staging registers --
+// round 2 prefetched the next image through 28 VGPRs per lane); a piece's tail beyond the image re-reads its last
+// 16 bytes into the slot's padding (the slot is padded to whole pieces, the padding is never read)
+template <int RU4, int NPIECE, int NW>
+__device__ __forceinline__ void rev_fetch(const u4* isrc, int c, float* slot, int wave, int lane) {
+    const u4* src = isrc + (int64_t)c * RU4;
+    for (int i = wave; i < NPIECE; i += NW) {
+        const int idx = i * 64 + lane;
+        __builtin_amdgcn_global_load_lds(src + (idx < RU4 ? idx : RU4 - 1), (lds_void*)(slot + i * 256), 16, 0, 0);
+    }
+}
+
+// The flush of a workgroup.  amax: this lane's largest accumulated term; wrapped(amax, nadds) says whether nadds such
+// terms may have left an accumulator's range -- the kernel flags it and the reduction poisons the result instead of
+// returning a wrong gradient.  acc_value(acc, k): fixed-point value of parameter k in layer block acc.  red: NW floats
+// of LDS nobody uses any more.
+template <int H, int L, int NW, class Wrapped, class AccValue>
+__device__ __forceinline__ void rev_flush(const FlowBwdArgs& a, int64_t m, int64_t mp, int64_t iters, float amax,
+                                          float glp_acc, float isc, const int* accb, float* red, int lane, int wave,
+                                          Wrapped wrapped, AccValue acc_value) {
+    typedef AccLayout<H, L> A_;
+    constexpr int D = 2 * H;
+    const int nl = 2 * a.S, U = a.U;
+    amax = wave_max(amax);
+    __syncthreads();
+    if (lane == 0) red[wave] = amax;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) amax = fmaxf(amax, red[w]);
+    if (wrapped(amax, (float)(iters * NW)) && threadIdx.x == 0) atomicOr(a.overflow, 1);
+    const int P = 2 * (H * U + U) + (L - 1) * 2 * (U * U + U) + 2 * (U * H + H);
+    const float tot = row16_sum(glp_acc);  // lanes 0..15 (q = 0) carried the terms
+    __syncthreads();
+    if (lane == 0) red[wave] = tot;
+    __syncthreads();
+    // this workgroup's fixed-point contribution, in the order of the gradient row: layer c -> [parameter block (P) |
+    // fold (2 D)]; flow_bwd_reduce_kernel adds the rows up
+    const int64_t nred = (a.Mp == 1 ? a.M : 1) * gridDim.x;
+    const int64_t blk = (a.Mp == 1 ? m : 0) * gridDim.x + blockIdx.x;
+    const int64_t prow = (int64_t)nl * (P + 2 * D);
+    int* dst = a.partials + (mp * nred + blk) * prow;
+    for (int i = threadIdx.x; i < nl * (P + 2 * D); i += NW * 64) {
+        const int c = i / (P + 2 * D);
+        const int k = i - c * (P + 2 * D);
+        const int* acc = accb + c * A_::INTS;
+        dst[i] = (k >= P) ? ((c & 1) ? acc[A_::o_fold + (k - P)] : 0) : acc_value(acc, k);
+    }
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) t += red[w];
+        a.glp_part[mp * nred + blk] = t * isc;
+    }
+}
+
 template <int H, int L, int NW, bool SPARE>
 __global__ void __launch_bounds__(NW * 64)
 flow_bwd_f16_kernel(FlowBwdArgs a) {
@@ -815,33 +861,11 @@ flow_bwd_f16_kernel(FlowBwdArgs a) {
     float* scrB = scrA + (kRevNScr - 1) * kScr;
     const u4* isrc = reinterpret_cast<const u4*>(a.rimg + mp * (int64_t)nl * R::FLOATS);
 
-    // layer image c -> ring slot by LDS-DMA (global_load_lds_dwordx4: 1 KB per wave-instruction, no staging registers --
-    // round 2 prefetched the next image through 28 VGPRs per lane); a piece's tail beyond the image re-reads its last
-    // 16 bytes into the slot's padding
-    typedef __attribute__((address_space(3))) void lds_void_;
-    auto fetch = [&](int c, float* slot) {
-        const u4* src = isrc + (int64_t)c * RU4;
-        for (int i = wave; i < NPIECE; i += NW) {
-            const int idx = i * 64 + lane;
-            __builtin_amdgcn_global_load_lds(src + (idx < RU4 ? idx : RU4 - 1), (lds_void_*)(slot + i * 256), 16, 0, 0);
-        }
-    };
+    auto fetch = [&](int c, float* slot) { rev_fetch<RU4, NPIECE, NW>(isrc, c, slot, wave, lane); };
     fetch(0, ring);
     for (int i = threadIdx.x; i < nl * ACC; i += NW * 64) accb[i] = 0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // power-of-two scale that brings max |g_lp| into [1, 2)
-    float sc = 1.f, isc = 1.f;
-    {
-        const float gm = __uint_as_float(*a.gmax);
-        if (gm > 0.f && gm < 3.0e38f) {
-            int e;
-            (void)frexpf(gm, &e);  // gm = f 2^e, f in [0.5, 1)
-            int k = 1 - e;
-            k = k > 120 ? 120 : (k < -120 ? -120 : k);
-            sc = ldexpf(1.f, k);
-            isc = ldexpf(1.f, -k);
-        }
-    }
+    const auto [sc, isc] = pow2_scale(__uint_as_float(*a.gmax));  // max |g_lp| into [1, 2)
     __syncthreads();
 
     const int64_t ntiles = (a.N + 15) >> 4;
@@ -917,45 +941,10 @@ flow_bwd_f16_kernel(FlowBwdArgs a) {
     // ---- flush ----
     // a term above the fixed-point budget may have wrapped an accumulator: flag it (the reduction then poisons the
     // result instead of returning a wrong gradient; the budget is 2^13 per term in units where max |g_log_prob| is 1..2)
-    float amax = fa.amax;
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    float* red = scr;  // the transposition scratch is free now
-    __syncthreads();
-    if (lane == 0) red[wave] = amax;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < NW; ++w) amax = fmaxf(amax, red[w]);
-    const bool wrapped = !(amax * (float)(iters * NW) < 2147483648.f);  // (also true for NaN / inf terms)
-    if (wrapped && threadIdx.x == 0) atomicOr(a.overflow, 1);
-    const int P = 2 * (H * U + U) + (L - 1) * 2 * (U * U + U) + 2 * (U * H + H);
-    float tot = glp_acc;
-    tot += __shfl_xor(tot, 1);
-    tot += __shfl_xor(tot, 2);
-    tot += __shfl_xor(tot, 4);
-    tot += __shfl_xor(tot, 8);  // lanes 0..15 (q = 0) carried the terms
-    __syncthreads();
-    if (lane == 0) red[wave] = tot;
-    __syncthreads();
-    {
-        // this workgroup's fixed-point contribution, in the order of the gradient row: layer c -> [parameter block (P) |
-        // fold (2 D)]; flow_bwd_reduce_kernel adds the rows up
-        const int64_t nred = (a.Mp == 1 ? a.M : 1) * gridDim.x;
-        const int64_t blk = (a.Mp == 1 ? m : 0) * gridDim.x + blockIdx.x;
-        const int64_t prow = (int64_t)nl * (P + 2 * D);
-        int* dst = a.partials + (mp * nred + blk) * prow;
-        for (int i = threadIdx.x; i < nl * (P + 2 * D); i += NW * 64) {
-            const int c = i / (P + 2 * D);
-            const int k = i - c * (P + 2 * D);
-            const int* acc = accb + c * ACC;
-            dst[i] = (k >= P) ? ((c & 1) ? acc[A_::o_fold + (k - P)] : 0) : acc[acc_src<H, L, SPARE>(k, U)];
-        }
-        if (threadIdx.x == 0) {
-            float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) t += red[w];
-            a.glp_part[mp * nred + blk] = t * isc;
-        }
-    }
+    rev_flush<H, L, NW>(
+        a, m, mp, iters, fa.amax, glp_acc, isc, accb, scr, lane, wave,
+        [](float amax, float nadds) { return !(amax * nadds < 2147483648.f); },  // (also true for NaN / inf terms)
+        [&](const int* acc, int k) { return acc[acc_src<H, L, SPARE>(k, U)]; });
 }
 
 }  // namespace tnf
@@ -997,18 +986,7 @@ coupling_bwd_f16_kernel(BwdArgs a) {
     const bool has_corr = !INV && a.gcorr != nullptr;
     const bool finalize = INV && a.g_lp != nullptr;  // last layer of a log_prob chain: seeds from the base density
     // the deltas are split into f16 halves: keep them clear of the f16 subnormals whatever the loss scale
-    float sc = 1.f, isc = 1.f;
-    if (a.gmax) {
-        const float gm = __uint_as_float(*a.gmax);
-        if (gm > 0.f && gm < 3.0e38f) {
-            int e;
-            (void)frexpf(gm, &e);
-            int k = 1 - e;
-            k = k > 120 ? 120 : (k < -120 ? -120 : k);
-            sc = ldexpf(1.f, k);
-            isc = ldexpf(1.f, -k);
-        }
-    }
+    const auto [sc, isc] = a.gmax ? pow2_scale(__uint_as_float(*a.gmax)) : Pow2Scale{1.f, 1.f};
     for (int i = threadIdx.x; i < 2 * D; i += NW * 64) {
         cst[i] = a.fold ? a.fold[mp * a.fold_stride + i] : (i < D ? 1.f : 0.f);
         cst[2 * D + i] = has_corr ? sc * a.gcorr[i] : 0.f;
@@ -1129,13 +1107,6 @@ coupling_bwd_f16_kernel(BwdArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) tile[j * 64 + lane] += v[j];
     };
-    auto red16 = [&](float v) -> float {
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
-        return v;
-    };
     for (int turn = 0; turn < NW; ++turn) {
         if (wave == turn) {
 #pragma unroll
@@ -1158,8 +1129,8 @@ coupling_bwd_f16_kernel(BwdArgs a) {
                 for (int mm = 0; mm < HT; ++mm)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float ax = red16(dAx[mm][j]), bx = red16(dBx[mm][j]);
-                        const float ay = red16(dAy[mm][j]), by = red16(dBy[mm][j]);
+                        const float ax = row16_sum(dAx[mm][j]), bx = row16_sum(dBx[mm][j]);
+                        const float ay = row16_sum(dAy[mm][j]), by = row16_sum(dBy[mm][j]);
                         if (s == 0) {
                             const int fx = c_off + 16 * mm + 4 * q + j, fy = t_off + 16 * mm + 4 * q + j;
                             gacc[A_::o_fold + fx] += ax;
@@ -1173,7 +1144,7 @@ coupling_bwd_f16_kernel(BwdArgs a) {
         __syncthreads();
     }
     if (finalize && a.glp_sum) {
-        const float tot = red16(glp_acc);
+        const float tot = row16_sum(glp_acc);
         if (lane == 0) atomicAdd(a.glp_sum + mp, tot * isc);
     }
     const int P = 2 * (H * U + U) + (L - 1) * 2 * (U * U + U) + 2 * (U * H + H);

@@ -33,7 +33,6 @@
 
 namespace tnf {
 
-typedef __attribute__((address_space(3))) void lds_void;
 // Tiles per wave and waves per workgroup.  Measured at D = 64, N = 2^19 (MI355X, steady state): 2 tiles x 8 waves
 // 0.583 ms (256 VGPRs, 55 spilled: the per-instruction issue cost of two waves per SIMD eats what the pairing saves),
 // 2 x 4 0.714 ms, the round-2 kernel (1 x 12, different accumulation) 0.555-0.594 ms.
@@ -426,29 +425,10 @@ flow_bwd_pair_kernel(FlowBwdArgs a) {
     float* scrB = scrA + (PL::NSCR - 1) * kScr;
     const u4* isrc = reinterpret_cast<const u4*>(a.rimg + mp * (int64_t)nl * R::FLOATS);
 
-    // layer image c -> ring slot: LDS-DMA, 1 KB per wave-instruction, no staging registers; a piece's tail beyond the
-    // image re-reads its last 16 bytes (the slot is padded to whole pieces, the padding is never read)
-    auto fetch = [&](int c, float* slot) {
-        const u4* src = isrc + (int64_t)c * RU4;
-        for (int i = wave; i < NPIECE; i += NW) {
-            const int idx = i * 64 + lane;
-            __builtin_amdgcn_global_load_lds(src + (idx < RU4 ? idx : RU4 - 1), (lds_void*)(slot + i * 256), 16, 0, 0);
-        }
-    };
+    auto fetch = [&](int c, float* slot) { rev_fetch<RU4, NPIECE, NW>(isrc, c, slot, wave, lane); };
     fetch(0, ring);
     for (int i = threadIdx.x; i < nl * ACC; i += NW * 64) accb[i] = 0;
-    float sc = 1.f, isc = 1.f;
-    {
-        const float gm = __uint_as_float(*a.gmax);
-        if (gm > 0.f && gm < 3.0e38f) {
-            int e;
-            (void)frexpf(gm, &e);  // gm = f 2^e, f in [0.5, 1)
-            int k = 1 - e;
-            k = k > 120 ? 120 : (k < -120 ? -120 : k);
-            sc = ldexpf(1.f, k);
-            isc = ldexpf(1.f, -k);
-        }
-    }
+    const auto [sc, isc] = pow2_scale(__uint_as_float(*a.gmax));  // max |g_lp| into [1, 2)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -549,45 +529,12 @@ flow_bwd_pair_kernel(FlowBwdArgs a) {
     // result instead of returning a wrong gradient.
     float amax = __builtin_fmaxf(fa.amax, __builtin_fmaxf(ma.hi - magic, magic - ma.lo) * a.fx);
     if (bad >= 0x7f800000u) amax = __builtin_inff();
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    float* red = scr;  // the transposition scratch is free now
-    __syncthreads();
-    if (lane == 0) red[wave] = amax;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < NW; ++w) amax = fmaxf(amax, red[w]);
-    const float nadds = (float)(iters * NW);
-    // 2^31: the int32 accumulators; 2^22: the magic-number form (also true for NaN / inf terms)
-    const bool wrapped = !(amax * nadds < 2147483648.f && amax < 4194304.f);
-    if (wrapped && threadIdx.x == 0) atomicOr(a.overflow, 1);
-    const int P = 2 * (H * U + U) + (L - 1) * 2 * (U * U + U) + 2 * (U * H + H);
-    float tot = glp_acc;
-    tot += __shfl_xor(tot, 1);
-    tot += __shfl_xor(tot, 2);
-    tot += __shfl_xor(tot, 4);
-    tot += __shfl_xor(tot, 8);  // lanes 0..15 (q = 0) carried the terms
-    __syncthreads();
-    if (lane == 0) red[wave] = tot;
-    __syncthreads();
-    {
-        const unsigned kmagic = (unsigned)(iters * NW) * __builtin_bit_cast(unsigned, magic);
-        const int64_t nred = (a.Mp == 1 ? a.M : 1) * gridDim.x;
-        const int64_t blk = (a.Mp == 1 ? m : 0) * gridDim.x + blockIdx.x;
-        const int64_t prow = (int64_t)nl * (P + 2 * D);
-        int* dst = a.partials + (mp * nred + blk) * prow;
-        for (int i = threadIdx.x; i < nl * (P + 2 * D); i += NW * 64) {
-            const int c = i / (P + 2 * D);
-            const int k = i - c * (P + 2 * D);
-            const int* acc = accb + c * ACC;
-            dst[i] = (k >= P) ? ((c & 1) ? acc[A_::o_fold + (k - P)] : 0) : acc_value_pair<H, L, SPARE>(acc, k, U, kmagic);
-        }
-        if (threadIdx.x == 0) {
-            float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) t += red[w];
-            a.glp_part[mp * nred + blk] = t * isc;
-        }
-    }
+    const unsigned kmagic = (unsigned)(iters * NW) * __builtin_bit_cast(unsigned, magic);
+    rev_flush<H, L, NW>(
+        a, m, mp, iters, amax, glp_acc, isc, accb, scr, lane, wave,
+        // 2^31: the int32 accumulators; 2^22: the magic-number form (also true for NaN / inf terms)
+        [](float amax, float nadds) { return !(amax * nadds < 2147483648.f && amax < 4194304.f); },
+        [&](const int* acc, int k) { return acc_value_pair<H, L, SPARE>(acc, k, U, kmagic); });
 }
 
 }  // namespace tnf

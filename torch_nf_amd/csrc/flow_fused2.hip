@@ -182,7 +182,7 @@ flow_fused2_kernel(Flow2Args a) {
         }
         if constexpr (FWD)
             for (int i = threadIdx.x; i < 2 * D; i += NWAVES * 64) fold[i] = i < D ? 1.f : 0.f;
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        acc = wave_sum(acc);
         if (lane == 0) red[wave] = acc;
         if (threadIdx.x == 0) *qhead = NWAVES;
         if (a.iv)
@@ -472,8 +472,7 @@ flow_fused2_kernel(Flow2Args a) {
             if constexpr (FWD) {
                 if (a.log_q) {  // density_estimator.py:369-372, 387: log_q = log N(omega; 0, I) - sum of the forward log-dets
                     double b = bsq[t];
-                    b += __shfl_xor(b, 16);
-                    b += __shfl_xor(b, 32);
+                    b = reduce_q(b);
                     if (q == 0 && row_ok)
                         a.log_q[m * a.N + row] = (-0.5 * b - (double)Dr * 0.91893853320467274178) - (double)ld_tot;
                 }
@@ -545,7 +544,6 @@ flow_fused2_kernel(Flow2Args a) {
 // the fold is owed to it and paid by the next launch, whose first layer transforms exactly that half (foldprev of
 // build_image2).  So an in-place middle launch reads 2 halves and writes 1: 392 B per sample instead of 520 at D = 64.
 // ---------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void lds_void2;
 
 struct Range2Args {
     Flow2Args f;
@@ -689,7 +687,7 @@ flow_range2_kernel(Range2Args ra) {
                 fold_inverse(a, prow, D, i / D, i % D, A, B, ld);
                 acc += ld;
             }
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        acc = wave_sum(acc);
         if (lane == 0) red[wave] = acc;
         if (threadIdx.x == 0) *qhead = NWAVES;
         __syncthreads();
@@ -731,7 +729,7 @@ flow_range2_kernel(Range2Args ra) {
                 fold_inverse(a, prow, D, i / D, i % D, A, B, ld);
                 acc += ld;
             }
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        acc = wave_sum(acc);
         if (lane == 0) red[wave] = acc;
         if (threadIdx.x == 0) *qhead = NWAVES;
         if (has_iv)
@@ -856,7 +854,7 @@ flow_range2_kernel(Range2Args ra) {
         if (ldi) {  // (uniform) one 4-byte copy per lane: lane l -> row l mod (16 NT) of the group
             int64_t row = g * (NT * 16) + (lane & (NT * 16 - 1));
             if (row >= a.N) row = a.N - 1;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned*>(ldi + row), (lds_void2*)(slot + GF), 4, 0, 0);
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned*>(ldi + row), (lds_void*)(slot + GF), 4, 0, 0);
         }
 #pragma unroll
         for (int k = 0; k < NI; ++k) {
@@ -869,7 +867,7 @@ flow_range2_kernel(Range2Args ra) {
 #endif
             int64_t row = g * (NT * 16) + r;
             if (row >= a.N) row = a.N - 1;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const u4*>(zb + row * D + (ch << 2)), (lds_void2*)(slot + k * 256), 16, 0,
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const u4*>(zb + row * D + (ch << 2)), (lds_void*)(slot + k * 256), 16, 0,
                                              (TNF2_RANGE_NTMEM & 1) ? 2 : 0);
         }
     };

@@ -86,7 +86,7 @@ flow_fused3_kernel(Flow2Args a) {
             fold[c * 2 * D + d] = A;
             fold[c * 2 * D + D + d] = mu - shift * A;
         }
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        acc = wave_sum(acc);
         if (lane == 0) red[wave] = acc;
         if (threadIdx.x == 0) *qhead = NWAVES;
         if (a.iv)

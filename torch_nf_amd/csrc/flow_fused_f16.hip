@@ -276,7 +276,7 @@ flow_fused_f16_kernel(FlowF16Args a) {
                 fold[c * 2 * D + d] = A;
                 fold[c * 2 * D + D + d] = B;
             }
-            for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+            acc = wave_sum(acc);
             if (lane == 0) red[wave] = acc;
         }
         if (threadIdx.x == 0) *qhead = NWAVES;

@@ -2,6 +2,7 @@
 // These are the coverage path: every shape the reference accepts runs here when
 // no MFMA specialisation exists (coupling_mfma.hip / flow_fused.hip hold those).
 #include "tnf_common.h"
+#include "wave_prims.h"
 
 namespace tnf {
 
@@ -11,19 +12,6 @@ namespace tnf {
 // the twin t/s MLP ping-pong through LDS; weights stream from global (L2).
 // Reference: bijectors.py:145-242.
 // ---------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ T tnf_tanh(T x);
-template <>
-__device__ __forceinline__ float tnf_tanh<float>(float x) { return tanhf(x); }
-template <>
-__device__ __forceinline__ double tnf_tanh<double>(double x) { return tanh(x); }
-template <typename T>
-__device__ __forceinline__ T tnf_exp(T x);
-template <>
-__device__ __forceinline__ float tnf_exp<float>(float x) { return expf(x); }
-template <>
-__device__ __forceinline__ double tnf_exp<double>(double x) { return exp(x); }
-
 template <typename T>
 __global__ void __launch_bounds__(256)
 coupling_generic_kernel(const T* __restrict__ z, const T* __restrict__ params, T* __restrict__ z_out,
@@ -79,8 +67,8 @@ coupling_generic_kernel(const T* __restrict__ z, const T* __restrict__ params, T
             acc_t += bias_t[o];
             acc_s += bias_s[o];
             if (l < L) {
-                acc_t = tnf_tanh<T>(acc_t);
-                acc_s = tnf_tanh<T>(acc_s);
+                acc_t = Mth<T>::tanh(acc_t);
+                acc_s = Mth<T>::tanh(acc_s);
             }
             bt[cur ^ 1][i * W + o] = acc_t;
             bs[cur ^ 1][i * W + o] = acc_s;
@@ -94,7 +82,7 @@ coupling_generic_kernel(const T* __restrict__ z, const T* __restrict__ params, T
         const T t = bt[cur][i * W + o];
         const T s = bs[cur][i * W + o];
         const T z2 = zt[(int64_t)i * D + t_off + o];
-        const T e = tnf_exp<T>(s);
+        const T e = Mth<T>::exp(s);
         zo[(int64_t)i * D + t_off + o] = inverse ? (z2 - t) / e : t + z2 * e;
     }
     if (tid < ts) {
@@ -157,7 +145,7 @@ affine_kernel(const T* __restrict__ z, const T* __restrict__ params, T* __restri
         const int64_t rem = idx - m * ND;
         const int d = (int)(rem % D);
         const T* p = params + (Mp == 1 ? 0 : m) * pstride;
-        const T scale = tnf_exp<T>(p[d]);
+        const T scale = Mth<T>::exp(p[d]);
         const T shift = p[D + d];
         const T v = z[(Mz == 1 ? 0 : m) * ND + rem];
         z_out[idx] = inverse ? (v - shift) / scale : scale * v + shift;
@@ -170,7 +158,7 @@ affine_logdet_kernel(const T* __restrict__ params, T* __restrict__ log_det, int 
     const T* p = params + (int64_t)blockIdx.x * pstride;
     T acc = 0;
     for (int d = threadIdx.x; d < D; d += 64) acc += p[d];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) log_det[blockIdx.x] = acc;
 }
 
@@ -222,7 +210,7 @@ __global__ void __launch_bounds__(64)
 bn_logdet_kernel(const float* __restrict__ alpha, float* __restrict__ log_det, int D) {
     float acc = 0.f;
     for (int d = threadIdx.x; d < D; d += 64) acc += logf(alpha[d]);
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) *log_det = -acc;
 }
 
@@ -478,7 +466,7 @@ base_log_density_kernel(const T* __restrict__ omega, double* __restrict__ out, i
         const T* w = omega + r * D;
         double acc = 0.0;
         for (int d = sub; d < D; d += 4) acc += (double)w[d] * (double)w[d];
-        acc += __shfl_xor(acc, 1);
+        acc += __shfl_xor(acc, 1);  // the row's 4 lanes: no wave_prims.h helper has this extent
         acc += __shfl_xor(acc, 2);
         if (sub == 0) out[r] = -0.5 * acc - (double)D * 0.91893853320467274178;
     }

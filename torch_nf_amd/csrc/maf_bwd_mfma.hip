@@ -95,17 +95,6 @@ __device__ void build_maf_bwd_images(float* fimg, float* timg, const float* __re
     }
 }
 
-// 16x16 transpose of an accumulator-layout tile through LDS (see coupling_bwd_mfma.hip)
-__device__ __forceinline__ f4 maf_transpose(f4 v, float* scr, int lane) {
-    const int s = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) scr[(4 * q + j) * 17 + s] = v[j];
-    f4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = scr[s * 17 + 4 * i + q];
-    return o;
-}
-
 struct MafBwdArgs {
     const float* z;
     const float* params;
@@ -162,18 +151,8 @@ maf_bwd_mfma_kernel(MafBwdArgs a, MafBLayout wl) {
     const bool fusedm = a.g_lp != nullptr;
     const bool has_iv = a.iv != nullptr;
     const bool fixedp = fusedm && a.gmax != nullptr;
-    float sc = 1.f, isc = 1.f, amax = 0.f;
-    if (fixedp) {
-        const float gm = __uint_as_float(*a.gmax);
-        if (gm > 0.f && gm < 3.0e38f) {
-            int e;
-            (void)frexpf(gm, &e);
-            int k = 1 - e;
-            k = k > 120 ? 120 : (k < -120 ? -120 : k);
-            sc = ldexpf(1.f, k);
-            isc = ldexpf(1.f, -k);
-        }
-    }
+    float amax = 0.f;
+    const auto [sc, isc] = fixedp ? pow2_scale(__uint_as_float(*a.gmax)) : Pow2Scale{1.f, 1.f};
     if (fusedm) {
         for (int i = threadIdx.x; i < 2 * D; i += 256) cst[i] = a.pre[mp * 2 * D + i];
         if (has_iv)
@@ -354,11 +333,11 @@ maf_bwd_mfma_kernel(MafBwdArgs a, MafBLayout wl) {
 #pragma unroll
                 for (int ui = 0; ui < UT; ++ui) {
                     const f4 hin = act_h(L, net, ui);
-                    const f4 h_t = rbf16_4(maf_transpose(hin, scrB, lane), bf);
+                    const f4 h_t = rbf16_4(transpose_tile(hin, scrB, lane), bf);
                     f4 acc = zero;
 #pragma unroll
                     for (int mo = 0; mo < DT; ++mo) {
-                        const f4 dt_ = maf_transpose(dlt[net][mo], scrA, lane);  // scrA holds one tile at a time
+                        const f4 dt_ = transpose_tile(dlt[net][mo], scrA, lane);  // scrA holds one tile at a time
                         f4 dw = zero;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) dw = mfma4(dt_[i], h_t[i], dw);  // D[o][k]
@@ -381,11 +360,11 @@ maf_bwd_mfma_kernel(MafBwdArgs a, MafBLayout wl) {
 #pragma unroll
                         for (int ui = 0; ui < UT; ++ui) {
                             const f4 hin = act_h(lev, net, ui);
-                            const f4 h_t = rbf16_4(maf_transpose(hin, scrB, lane), bf);
+                            const f4 h_t = rbf16_4(transpose_tile(hin, scrB, lane), bf);
                             f4 acc = zero;
 #pragma unroll
                             for (int uo = 0; uo < UT; ++uo) {
-                                const f4 dt_ = maf_transpose(dprev[net][uo], scrA, lane);
+                                const f4 dt_ = transpose_tile(dprev[net][uo], scrA, lane);
                                 f4 dw = zero;
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) dw = mfma4(dt_[i], h_t[i], dw);
@@ -407,13 +386,13 @@ maf_bwd_mfma_kernel(MafBwdArgs a, MafBLayout wl) {
             // layer 0: inputs = x (DT tiles), outputs = hidden level 0 (UT tiles)
 #pragma unroll
             for (int mm = 0; mm < DT; ++mm) {
-                const f4 x_t = maf_transpose(xo[mm], scrB, lane);
+                const f4 x_t = transpose_tile(xo[mm], scrB, lane);
                 f4 acc = zero;
 #pragma unroll
                 for (int net = 0; net < 2; ++net) {
 #pragma unroll
                     for (int ut = 0; ut < UT; ++ut) {
-                        const f4 dt_ = maf_transpose(dprev[net][ut], scrA, lane);
+                        const f4 dt_ = transpose_tile(dprev[net][ut], scrA, lane);
                         f4 dw = zero;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) dw = mfma4(dt_[i], x_t[i], dw);
@@ -459,7 +438,7 @@ maf_bwd_mfma_kernel(MafBwdArgs a, MafBLayout wl) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float va = fdA[mm][j] * isc, vb = fdB[mm][j] * isc;
-                for (int off = 8; off > 0; off >>= 1) {
+                for (int off = 8; off > 0; off >>= 1) {  // 8 -> 1: not row16_sum's order (1 -> 8), left as it is
                     va += __shfl_xor(va, off);
                     vb += __shfl_xor(vb, off);
                 }
@@ -469,7 +448,7 @@ maf_bwd_mfma_kernel(MafBwdArgs a, MafBLayout wl) {
                     atomicAdd(red + D + f, vb);
                 }
             }
-        for (int off = 8; off > 0; off >>= 1) glp_acc += __shfl_xor(glp_acc, off);
+        for (int off = 8; off > 0; off >>= 1) glp_acc += __shfl_xor(glp_acc, off);  // (8 -> 1 as above)
         if (lane == 0) atomicAdd(red + 2 * D, glp_acc * isc);
         __syncthreads();
         const bool own_row = a.Mp > 1 && gridDim.x == 1;
@@ -488,7 +467,7 @@ maf_bwd_mfma_kernel(MafBwdArgs a, MafBLayout wl) {
         const bool own = a.Mp > 1 && gridDim.x == 1;
         float poison = 0.f, unfx = 1.f;
         if (fixedp) {  // a term beyond the budget may have wrapped an accumulator: poison instead of returning it
-            for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+            amax = wave_max(amax);
             float* pr = scr_all;
             if (lane == 0) pr[wave] = amax;
             __syncthreads();
@@ -583,7 +562,7 @@ maf_gmax_kernel(const float* __restrict__ g, int64_t n, unsigned* __restrict__ o
     __shared__ float red[4];
     float m = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(g[i]));
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {

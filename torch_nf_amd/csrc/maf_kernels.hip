@@ -11,19 +11,6 @@
 
 namespace tnf {
 
-template <typename T>
-__device__ __forceinline__ T maf_tanh(T x);
-template <>
-__device__ __forceinline__ float maf_tanh<float>(float x) { return tanhf(x); }
-template <>
-__device__ __forceinline__ double maf_tanh<double>(double x) { return tanh(x); }
-template <typename T>
-__device__ __forceinline__ T maf_exp(T x);
-template <>
-__device__ __forceinline__ float maf_exp<float>(float x) { return expf(x); }
-template <>
-__device__ __forceinline__ double maf_exp<double>(double x) { return exp(x); }
-
 // one evaluation of the twin masked nets on the tile: input zin [TS][W] -> mu, alpha in bm[cur], ba[cur]
 template <typename T>
 __device__ __forceinline__ int maf_net(const T* __restrict__ params, const T* __restrict__ masks, const T* zin,
@@ -54,8 +41,8 @@ __device__ __forceinline__ int maf_net(const T* __restrict__ params, const T* __
                 aa += xa[i * W + k] * (mv * wa[(int64_t)k * dout + o]);
             }
             if (l < L) {
-                am = maf_tanh<T>(am);
-                aa = maf_tanh<T>(aa);
+                am = Mth<T>::tanh(am);
+                aa = Mth<T>::tanh(aa);
             }
             om[i * W + o] = am;
             oa[i * W + o] = aa;
@@ -96,7 +83,7 @@ maf_kernel(const T* __restrict__ z, const T* __restrict__ params, const T* __res
         const int cur = maf_net<T>(p, masks, zc, bm[0], bm[1], ba[0], ba[1], ts, D, L, U, W, tid);
         for (int idx = tid; idx < ts * D; idx += 256) {
             const int i = idx / D, d = idx - i * D;
-            zo[(int64_t)i * D + d] = (zc[i * W + d] - bm[cur][i * W + d]) / maf_exp<T>(ba[cur][i * W + d]);
+            zo[(int64_t)i * D + d] = (zc[i * W + d] - bm[cur][i * W + d]) / Mth<T>::exp(ba[cur][i * W + d]);
             if (alpha_out) alpha_out[(m * N + n0 + i) * D + d] = ba[cur][i * W + d];  // per-dimension f_alpha(z)
         }
         if (tid < ts) {
@@ -110,7 +97,7 @@ maf_kernel(const T* __restrict__ z, const T* __restrict__ params, const T* __res
             cur = maf_net<T>(p, masks, zc, bm[0], bm[1], ba[0], ba[1], ts, D, L, U, W, tid);
             for (int idx = tid; idx < ts * D; idx += 256) {
                 const int i = idx / D, d = idx - i * D;
-                zc[i * W + d] = zt[(int64_t)i * D + d] * maf_exp<T>(ba[cur][i * W + d]) + bm[cur][i * W + d];
+                zc[i * W + d] = zt[(int64_t)i * D + d] * Mth<T>::exp(ba[cur][i * W + d]) + bm[cur][i * W + d];
             }
             __syncthreads();
         }
@@ -260,8 +247,8 @@ maf_backward_kernel(const T* __restrict__ z, const T* __restrict__ params, const
                     aa += xa[i * W + k] * (mv * wa[(int64_t)k * dout + o]);
                 }
                 if (l < L) {
-                    am = maf_tanh<T>(am);
-                    aa = maf_tanh<T>(aa);
+                    am = Mth<T>::tanh(am);
+                    aa = Mth<T>::tanh(aa);
                 }
                 om[i * W + o] = am;
                 oa[i * W + o] = aa;
@@ -274,7 +261,7 @@ maf_backward_kernel(const T* __restrict__ z, const T* __restrict__ params, const
     for (int idx = tid; idx < ts * D; idx += 256) {
         const int i = idx / D, d = idx - i * D;
         const T mu = outb[i * W + d], al = outb[plane + i * W + d];
-        const T em = maf_exp<T>(-al);
+        const T em = Mth<T>::exp(-al);
         const T g = gzo[(int64_t)i * D + d];
         const T gl = g_ld[m * N + n0 + i];
         const T dz = g * em;

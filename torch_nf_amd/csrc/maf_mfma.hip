@@ -243,7 +243,7 @@ ar_fold_kernel(const float* __restrict__ params, int64_t pstride, int64_t p_maf,
         fold[m * 2 * D + d] = A;
         fold[m * 2 * D + D + d] = B;
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) ldc[m] = acc;
 }
 

@@ -31,32 +31,9 @@
 //   Per tanh that leaves v_exp_f32, v_add_f32, v_rcp_f32; per transformed feature
 //   v_sub/v_exp/v_mul (+ the log-det add).
 #pragma once
-#include <hip/hip_runtime.h>
-
-#ifndef TNF_ABLATE
-#define TNF_ABLATE 0
-#endif
+#include "wave_prims.h"
 
 namespace tnf {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-constexpr float kLog2e = 1.44269504088896340736f;
-constexpr float kTwoLog2e = 2.88539008177792681472f;
-constexpr float kLn2 = 0.69314718055994530942f;
-
-// r = 1/(2^a + 1)  (a = 2 log2(e) x  ->  tanh(x) = 1 - 2r).  2^a -> inf gives r = 0, -> 0 gives r = 1.
-__device__ __forceinline__ float sig2(float a) {
-#if TNF_ABLATE == 1
-    return a;  // timing experiment only: no transcendental work
-#else
-    return __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(a) + 1.0f);
-#endif
-}
 
 // The bf16 experiment on the fp32-MFMA kernels (TNF_OPT_OPERAND_PREC = 1): operands rounded to bf16 (RNE) and widened
 // back.  The products of two such values are exact in fp32, so feeding them to the fp32 MFMA reproduces a bf16 MFMA
@@ -79,13 +56,6 @@ __device__ __forceinline__ f4 sig2_4(f4 v) {
     r[2] = sig2(v[2]);
     r[3] = sig2(v[3]);
     return r;
-}
-
-// sum over the four q-lanes that share a sample / an operand row (lanes r, r+16, r+32, r+48)
-__device__ __forceinline__ float reduce_q(float v) {
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    return v;
 }
 
 // Unconditional load + select: a predicated `ok ? p[i] : 0` makes hipcc branch around every

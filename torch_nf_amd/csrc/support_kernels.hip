@@ -9,22 +9,6 @@
 
 namespace tnf {
 
-template <typename T> struct Mth;
-template <> struct Mth<float> {
-    static __device__ __forceinline__ float tanh(float x) { return tanhf(x); }
-    static __device__ __forceinline__ float exp(float x) { return expf(x); }
-    static __device__ __forceinline__ float log(float x) { return logf(x); }
-    static __device__ __forceinline__ float log1p(float x) { return log1pf(x); }
-    static __device__ __forceinline__ float abs(float x) { return fabsf(x); }
-};
-template <> struct Mth<double> {
-    static __device__ __forceinline__ double tanh(double x) { return ::tanh(x); }
-    static __device__ __forceinline__ double exp(double x) { return ::exp(x); }
-    static __device__ __forceinline__ double log(double x) { return ::log(x); }
-    static __device__ __forceinline__ double log1p(double x) { return ::log1p(x); }
-    static __device__ __forceinline__ double abs(double x) { return fabs(x); }
-};
-
 // torch.nn.functional.softplus (beta 1, threshold 20) and logsigmoid as torch evaluates them
 template <typename T>
 __device__ __forceinline__ T softplus_t(T x) { return x > (T)20 ? x : Mth<T>::log1p(Mth<T>::exp(x)); }

@@ -9,12 +9,6 @@
 
 namespace tnf {
 
-__device__ __forceinline__ float sm_exp(float x) { return __builtin_amdgcn_exp2f(kLog2e * x); }
-__device__ __forceinline__ float sm_log(float x) { return kLn2 * __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float sm_tanh(float x) { return 1.f - 2.f * sig2(kTwoLog2e * x); }
-// log(sigmoid(x)) = min(x, 0) - log(1 + exp(-|x|))
-__device__ __forceinline__ float sm_logsigmoid(float x) { return fminf(x, 0.f) - sm_log(1.f + sm_exp(-fabsf(x))); }
-
 // INV: x is a point of the constrained space; out = its pre-image, ld = the FORWARD log-det there (the
 // reference's convention, :529-553).  !INV: forward map and its log-det (:509-527).
 template <bool INV>
@@ -28,20 +22,20 @@ __device__ __forceinline__ void interval_fast(float x, const float* c, int DP, i
         float zi = x;
         if (INV) {
             const float u = (x - tc) * __builtin_amdgcn_rcpf(tm);
-            zi = 0.5f * (sm_log(1.f + u + eps) - sm_log(1.f - u + eps));  // torch_atanh, :555-557
+            zi = 0.5f * (fast_log(1.f + u + eps) - fast_log(1.f - u + eps));  // torch_atanh, :555-557
         }
-        const float t = sm_tanh(zi);
-        ld = ltm + sm_log(1.f - t * t + eps);
+        const float t = fast_tanh(zi);
+        ld = ltm + fast_log(1.f - t * t + eps);
         out = INV ? zi : tm * t + tc;
     } else if (sf != 0.f) {
         const float sm = c[4 * DP + d], sc = c[5 * DP + d];
         if (INV) {
-            const float zi = sm_log(sm_exp((x - sc) * sm) - 1.f + eps);  // softplus_m is +-1: division = product
+            const float zi = fast_log(fast_exp((x - sc) * sm) - 1.f + eps);  // softplus_m is +-1: division = product
             out = zi;
-            ld = sm_logsigmoid(zi);
+            ld = fast_logsigmoid(zi);
         } else {
-            out = sm * (fmaxf(x, 0.f) + sm_log(1.f + sm_exp(-fabsf(x)))) + sc;
-            ld = sm_logsigmoid(x);
+            out = sm * (fmaxf(x, 0.f) + fast_log(1.f + fast_exp(-fabsf(x)))) + sc;
+            ld = fast_logsigmoid(x);
         }
     }
 }

@@ -27,6 +27,24 @@ inline dim3 grid_xm(int64_t bx, int64_t M) {
 }
 #if defined(__HIPCC__)
 __device__ __forceinline__ int64_t grid_m() { return (int64_t)blockIdx.y + (int64_t)gridDim.y * (int64_t)blockIdx.z; }
+
+// libm in the kernel's element type: the one float / double trait of the dtype-generic kernels (generic, backward,
+// MAF and support kernels).  The fp32 MFMA kernels use the hardware forms of wave_prims.h instead.
+template <typename T> struct Mth;
+template <> struct Mth<float> {
+    static __device__ __forceinline__ float tanh(float x) { return tanhf(x); }
+    static __device__ __forceinline__ float exp(float x) { return expf(x); }
+    static __device__ __forceinline__ float log(float x) { return logf(x); }
+    static __device__ __forceinline__ float log1p(float x) { return log1pf(x); }
+    static __device__ __forceinline__ float abs(float x) { return fabsf(x); }
+};
+template <> struct Mth<double> {
+    static __device__ __forceinline__ double tanh(double x) { return ::tanh(x); }
+    static __device__ __forceinline__ double exp(double x) { return ::exp(x); }
+    static __device__ __forceinline__ double log(double x) { return ::log(x); }
+    static __device__ __forceinline__ double log1p(double x) { return ::log1p(x); }
+    static __device__ __forceinline__ double abs(double x) { return fabs(x); }
+};
 #endif
 
 // ---- packed parameter layout of one RealNVP layer (bijectors.py:222-242) ---
