@@ -13,11 +13,11 @@ from . import (bijectors, conditional_density_estimator, density_estimator, erro
                lfi, systems)
 from .bijectors import MAF, ToInterval, ToSimplex, Affine, BatchNorm, Bijector, RealNVP
 from .conditional_density_estimator import ConditionalDensityEstimator
-from .density_estimator import DensityEstimator, NormFlow
+from .density_estimator import DensityEstimator, MoG, NormFlow
 from .exponential_families import MVN, Dirichlet, ExponentialFamily
 
 __version__ = "0.1.0"
-__all__ = ["Bijector", "RealNVP", "MAF", "ToInterval", "ToSimplex", "Affine", "BatchNorm", "DensityEstimator", "NormFlow",
+__all__ = ["Bijector", "RealNVP", "MAF", "ToInterval", "ToSimplex", "Affine", "BatchNorm", "DensityEstimator", "NormFlow", "MoG",
            "ConditionalDensityEstimator", "ExponentialFamily", "MVN", "Dirichlet", "exponential_families",
            "install_as_torch_nf"]
 

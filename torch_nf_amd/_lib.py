@@ -29,6 +29,7 @@ DIAG_FLOW_PADDED, DIAG_FLOW_PADDED_FWD = 16, 17
 DIAG_FAMILIES = 18
 EF_MVN, EF_DIRICHLET = 0, 1
 EF_COUNT_DOT, EF_COUNT_DOT_BWD = 0, 1  # tnf_ef_launch_count
+MOG_COUNT_LOGPROB, MOG_COUNT_LOGPROB_BWD, MOG_COUNT_SAMPLE = 0, 1, 2  # tnf_mog_launch_count
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
@@ -154,6 +155,19 @@ SIGNATURES = {
     "tnf_ef_dot_backward": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _vp, _i64, _vp]),
 }
 
+# the mixture-of-Gaussians family, declared in include/tnf_mog.h: a table of its own, because every entry of SIGNATURES
+# has its rows in the pinned host tables of tnf.h (tests/test_mog_host.py keeps this one in step with its header)
+MOG_SIGNATURES = {
+    "tnf_mog_num_params": (_i64, [_i32, _i32]),
+    "tnf_mog_supported": (ctypes.c_int, [_i32, _i32]),
+    "tnf_mog_launch_count": (_i64, [_i32]),
+    "tnf_mog_log_prob_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i64, _vp]),
+    "tnf_mog_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32]),
+    "tnf_mog_log_prob_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i64,
+                                                      _vp, _i64, _vp]),
+    "tnf_mog_sample_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -163,7 +177,7 @@ def _load():
             "There is no non-HIP fallback." % LIB_PATH
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(MOG_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError here = header / library out of step
         fn.restype = res
         fn.argtypes = args

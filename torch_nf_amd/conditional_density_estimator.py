@@ -4,8 +4,9 @@ Drop-in for torch_nf/conditional_density_estimator.py:10-104 of the reference: a
 nn.Module whose `param_net` (stock torch.nn Linear/Tanh[/Dropout] stack -- it runs on
 hipBLASLt when the module lives on the GPU and is NOT re-implemented here) maps a
 context x (M, D_x) to one flat flow-parameter row per context (M, D_params); sampling
-and density evaluation are delegated to the wrapped NormFlow, i.e. to the HIP kernels
-with per-context weights (M_p = M).
+and density evaluation are delegated to the wrapped NormFlow or MoG, i.e. to the HIP kernels
+with per-context weights (M_p = M).  A MoG always takes the materialised param_net -> `mog.log_prob` path: the fused
+conditioner kernels are the coupling flow's.
 """
 from collections import OrderedDict
 
@@ -57,7 +58,7 @@ def _pos_dparams(val):
 
 
 class ConditionalDensityEstimator(torch.nn.Module):
-    """:param density_estimator: a NormFlow built with conditioner=True (exact type, as in
+    """:param density_estimator: a NormFlow or a MoG built with conditioner=True (exact types, as in
     the reference :48-49).  :param D_x: context width.  :param hidden_layers: list of
     hidden widths of param_net.  :param dropout: add nn.Dropout after every activation."""
 
@@ -95,7 +96,7 @@ class ConditionalDensityEstimator(torch.nn.Module):
 
     @density_estimator.setter
     def density_estimator(self, val):
-        if type(val) not in [de.NormFlow]:
+        if type(val) not in [de.NormFlow, de.MoG]:
             from .error_formatters import format_type_err_msg
             raise TypeError(format_type_err_msg(self, "density_estimator", val, de.DensityEstimator))
         self.__dict__["_cde_flow"] = val
@@ -146,7 +147,9 @@ class ConditionalDensityEstimator(torch.nn.Module):
             z, sld = self._fused_sampling(x, o64.float())
             return self._home(x, z, ops.base_log_density_f64(o64) - sld)
         params = self._params_for(x)
-        return self.density_estimator(N=N, params=params, freeze_bn=freeze_bn)
+        if type(self.density_estimator) is de.NormFlow:  # conditional_density_estimator.py:95-98
+            return self.density_estimator(N=N, params=params, freeze_bn=freeze_bn)
+        return self.density_estimator(N=N, params=params)
 
     def sample(self, x, N=100, freeze_bn=True, generator=None):
         """Extension (not in the reference): like `__call__`, but the base draw comes from the device RNG
@@ -158,7 +161,9 @@ class ConditionalDensityEstimator(torch.nn.Module):
             z, sld = self._fused_sampling(x, omega)
             return self._home(x, z, ops.base_log_density_f64(omega) - sld)
         params = self._params_for(x)
-        return self.density_estimator.sample(N, params, freeze_bn=freeze_bn, generator=generator)
+        if type(self.density_estimator) is de.NormFlow:
+            return self.density_estimator.sample(N, params, freeze_bn=freeze_bn, generator=generator)
+        return self.density_estimator.sample(N, params, generator=generator)
 
     def _home(self, x, z, log_q):
         home = next(self.param_net.parameters()).device  # where NormFlow would return them: the parameters' device
@@ -170,7 +175,7 @@ class ConditionalDensityEstimator(torch.nn.Module):
         kernel covers."""
         nf = self.density_estimator
         last = self.param_net[-1]
-        return (self.fuse_conditioner and nf.arch_type == "coupling" and nf.support_layer is None
+        return (self.fuse_conditioner and type(nf) is de.NormFlow and nf.arch_type == "coupling" and nf.support_layer is None
                 and not nf._stats_in_graph() and x.dtype == torch.float32 and last.weight.dtype == torch.float32
                 and ops.cond_flow_supported(nf.D, nf.num_stages, nf.num_layers, nf.num_units, last.in_features))
 

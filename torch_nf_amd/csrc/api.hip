@@ -21,6 +21,11 @@ void ef_count(int which) {
     if (which >= 0 && which < TNF_EF_COUNTERS) g_ef_launches[which].fetch_add(1, std::memory_order_relaxed);
 }
 
+static std::atomic<long long> g_mog_launches[TNF_MOG_COUNTERS];
+void mog_count(int which) {
+    if (which >= 0 && which < TNF_MOG_COUNTERS) g_mog_launches[which].fetch_add(1, std::memory_order_relaxed);
+}
+
 char* err_buf() {
     static thread_local char buf[512] = {0};
     return buf;
@@ -852,6 +857,71 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
         if (int rc = check_workspace(fn, workspace, workspace_bytes, need)) return rc;
     }
     return launch_ef_dot_backward(dtype, family, z, eta, g_out, g_z, g_eta, M, N, D, ld_eta, workspace, as_stream(stream));
+}
+
+// ---- mixture of Gaussians (mog_kernels.hip; include/tnf_mog.h) ----
+int64_t tnf_mog_num_params(int32_t D, int32_t K) {
+    const int64_t n = mog_num_params(D, K);
+    if (n < 0) return fail(TNF_EINVAL, "tnf_mog_num_params: D=%d K=%d", D, K);
+    return n;
+}
+
+int tnf_mog_supported(int32_t D, int32_t K) { return mog_fused_supported(D, K) ? 1 : 0; }
+
+int64_t tnf_mog_launch_count(int32_t which) {
+    if (which < 0 || which >= TNF_MOG_COUNTERS) return fail(TNF_EINVAL, "tnf_mog_launch_count: counter %d", which);
+    return g_mog_launches[which].load(std::memory_order_relaxed);
+}
+
+// what the three compute entries share: the shape, the batch, the row length
+static int mog_check(const char* fn, int64_t M_z, int64_t M_p, int64_t N, int32_t D, int32_t K, int64_t ld_params) {
+    const int64_t need = mog_num_params(D, K);
+    if (need < 0) return fail(TNF_EINVAL, "%s: D=%d K=%d", fn, D, K);
+    if (int rc = check_mnd(fn, M_z, M_p, N, D)) return rc;
+    if (M_p != 1 && M_p != (M_z > M_p ? M_z : M_p))
+        return fail(TNF_EINVAL, "%s: M_p=%lld is neither 1 nor M=%lld", fn, (long long)M_p, (long long)M_z);
+    if (ld_params < need)
+        return fail(TNF_EINVAL, "%s: params row has %lld elements, MoG(D=%d, K=%d) needs %lld", fn, (long long)ld_params, D, K,
+                    (long long)need);
+    return TNF_OK;
+}
+
+int tnf_mog_log_prob_f32(const float* z, const float* params, const float* bounds, float* lp, int64_t M_z, int64_t M_p,
+                         int64_t N, int32_t D, int32_t K, int64_t ld_params, void* stream) {
+    const char* fn = "tnf_mog_log_prob_f32";
+    if (int rc = mog_check(fn, M_z, M_p, N, D, K, ld_params)) return rc;
+    if (!z || !params || !lp) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
+    return launch_mog_log_prob(z, params, bounds, lp, M_z, M_p, N, D, K, ld_params, as_stream(stream));
+}
+
+int64_t tnf_mog_bwd_workspace_bytes(int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t K) {
+    if (bad_batch(M, M_p, N) || mog_num_params(D, K) < 0)
+        return fail(TNF_EINVAL, "tnf_mog_bwd_workspace_bytes: M=%lld M_p=%lld N=%lld D=%d K=%d", (long long)M, (long long)M_p,
+                    (long long)N, D, K);
+    return mog_bwd_workspace(M, M_p, N, D, K);
+}
+
+int tnf_mog_log_prob_backward_f32(const float* z, const float* params, const float* bounds, const float* g_lp, float* g_z,
+                                  float* g_params, int64_t M_z, int64_t M_p, int64_t N, int32_t D, int32_t K,
+                                  int64_t ld_params, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "tnf_mog_log_prob_backward_f32";
+    if (int rc = mog_check(fn, M_z, M_p, N, D, K, ld_params)) return rc;
+    if (!z || !params || !g_lp || !g_params) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
+    const int64_t need = mog_bwd_workspace(M_z > M_p ? M_z : M_p, M_p, N, D, K);
+    if (need > 0) {
+        if (int rc = check_workspace(fn, workspace, workspace_bytes, need)) return rc;
+        if (!aligned16(workspace)) return fail(TNF_EINVAL, "%s: workspace must be 16-byte aligned", fn);
+    }
+    return launch_mog_log_prob_backward(z, params, bounds, g_lp, g_z, g_params, M_z, M_p, N, D, K, ld_params, workspace,
+                                        as_stream(stream));
+}
+
+int tnf_mog_sample_f32(const float* params, const float* bounds, const float* u, const float* e1, const float* e2, float* z,
+                       float* log_q, int64_t M, int64_t N, int32_t D, int32_t K, int64_t ld_params, void* stream) {
+    const char* fn = "tnf_mog_sample_f32";
+    if (int rc = mog_check(fn, M, M, N, D, K, ld_params)) return rc;
+    if (!params || !u || !e1 || !e2 || !z || !log_q) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
+    return launch_mog_sample(params, bounds, u, e1, e2, z, log_q, M, N, D, K, ld_params, as_stream(stream));
 }
 
 int tnf_base_log_density_f64(int32_t dtype, const void* omega, double* out, int64_t rows, int32_t D,

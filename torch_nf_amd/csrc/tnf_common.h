@@ -349,6 +349,18 @@ int launch_ef_dot(int dtype, int family, const void* z, const void* eta, void* o
                   int64_t ld_eta, hipStream_t st);
 int launch_ef_dot_backward(int dtype, int family, const void* z, const void* eta, const void* g_out, void* g_z,
                            void* g_eta, int64_t M, int64_t N, int D, int64_t ld_eta, void* ws, hipStream_t st);
+// mixture of Gaussians (mog_kernels.hip): log_prob, its backward, sampling with log_q
+int64_t mog_num_params(int D, int K);  // -1: D < 2, D > TNF_MOG_MAX_D, K < 1 or a row of 2^30 floats and more
+bool mog_fused_supported(int D, int K);
+void mog_count(int which);  // api.hip: launch counters behind tnf_mog_launch_count
+int64_t mog_bwd_workspace(int64_t M, int64_t Mp, int64_t N, int D, int K);
+int launch_mog_log_prob(const float* z, const float* params, const float* bounds, float* lp, int64_t Mz, int64_t Mp,
+                        int64_t N, int D, int K, int64_t ld, hipStream_t st);
+int launch_mog_log_prob_backward(const float* z, const float* params, const float* bounds, const float* g_lp, float* g_z,
+                                 float* g_params, int64_t Mz, int64_t Mp, int64_t N, int D, int K, int64_t ld, void* ws,
+                                 hipStream_t st);
+int launch_mog_sample(const float* params, const float* bounds, const float* u, const float* e1, const float* e2, float* z,
+                      float* log_q, int64_t M, int64_t N, int D, int K, int64_t ld, hipStream_t st);
 // MAF on the matrix pipe (maf_mfma.hip): float32, D <= 64, U <= 64, L <= 5
 struct MafArgs {
     const float* z;

@@ -506,3 +506,168 @@ class NormFlow(DensityEstimator):
             log_q = torch.sum(-(z0 ** 2), axis=2) / 2.0 - self.D * np.log(np.sqrt(2.0 * np.pi))
             log_q = log_q - sum_log_det
         return log_q if ld_support is None else log_q - ld_support
+
+
+def _pos_k(val):
+    if val < 1:
+        raise ValueError("MoG K %d must be greater than 0." % val)
+    return val
+
+
+MOG_EPS = 1e-12
+
+
+class MoG(DensityEstimator):
+    """Mixture of K Gaussians (density_estimator.py:57-237), on the kernels of csrc/mog_kernels.hip.
+
+    One parameter row is [logits (K) | mu_raw (K, D) | u (K, D(D+1)/2)]: alpha = softmax(logits), U_k upper triangular
+    from the packed row-major triangle u with U_ii = exp(u_ii), Sigma_inv_k = U_k^T U_k.  With both `lb` and `ub`
+    (length-D arrays; m = (ub - lb)/2, c = (ub + lb)/2): mu = m tanh(mu_raw) + c, U_ii = exp(u_ii)/sqrt(m_i).
+    `log_prob` is the reference's formula with its EPS = 1e-12 terms -- for K > 1 it saturates at log EPS = -27.63 --
+    evaluated in the log domain, so it is the float64 value of that formula to float32 rounding at every D.  float32 only.
+
+    Sampling: `forward` / `__call__` take their draws from np.random in the fixed order u (M, N), e1, e2 (M, N, D), so
+    np.random.seed reproduces a call; component k = #{j : cumsum(alpha)_j <= u}, z = mu_k + U_k^-1 e1 + sqrt(0.001) e2,
+    which is the reference's N(mu_k, Sigma_k + 0.001 I) (:152).  One deviation: the log_q beside the samples is this
+    class's `log_prob(z, params)` (written by the sampling kernel), where the reference evaluates `log_prob_np`, whose
+    only EPS is the one inside the final log.  Samples carry no gradient (the reference detaches there too).
+
+    Extra (not in the reference): `device`, `_forward_from` (injected draws), `sample` (device-side draws)."""
+
+    K = _Checked("K", int, _pos_k)
+
+    def __init__(self, D, conditioner=False, K=1, lb=None, ub=None, device=None):
+        super().__init__(D, conditioner)
+        self.K = K
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
+                else torch.device("cpu")
+        self.device = torch.device(device)
+        self.count_num_params()
+        if not self.conditioner:
+            self._param_init()
+        self.lb = lb
+        self.ub = ub
+
+    def count_num_params(self):
+        """density_estimator.py:235-237."""
+        self.D_params = self.K * (1 + self.D + self.D * (self.D + 1) // 2)
+
+    def _param_init(self):
+        """xavier_normal_ on a (1, D_params) row (:84-88), drawn on the host, then moved, as NormFlow does."""
+        init = torch.nn.init.xavier_normal_(torch.zeros(1, self.D_params))
+        self.params = init.to(self.device).requires_grad_(True)
+        return None
+
+    def _has_bounds(self):
+        return (self.lb is not None) and (self.ub is not None)
+
+    def _bounds(self):
+        """None, or the (2, D) float32 [lb | ub] block the kernels take (rebuilt when lb / ub were replaced)."""
+        if not self._has_bounds():
+            return None
+        cached = self.__dict__.get("_bounds_cache")
+        if cached is None or cached[0] is not self.lb or cached[1] is not self.ub:
+            lb, ub = np.asarray(self.lb, dtype=np.float64), np.asarray(self.ub, dtype=np.float64)
+            if lb.shape != (self.D,) or ub.shape != (self.D,):
+                raise ValueError("MoG lb and ub must have shape (%d,), got %s and %s" % (self.D, lb.shape, ub.shape))
+            if not np.all(ub > lb):
+                raise ValueError("MoG ub must exceed lb in every dimension.")
+            cached = (self.lb, self.ub, torch.tensor(np.stack([lb, ub]), dtype=torch.float32))
+            self.__dict__["_bounds_cache"] = cached
+        return cached[2]
+
+    def _device_bounds(self):
+        """`_bounds()` on the compute device: one copy per device, made once (like ToInterval's constants), so that no
+        call copies from the host -- a host copy would synchronise and could not be captured into a HIP graph."""
+        dev = _lib.require_device()
+        host = self._bounds()
+        if host is None:
+            return None
+        cached = self.__dict__.get("_bounds_dev")
+        if cached is None or cached[0] is not host or cached[1] != dev:
+            cached = (host, dev, host.to(dev))
+            self.__dict__["_bounds_dev"] = cached
+        return cached[2]
+
+    def _get_MoG_params(self, params, numpy=False):
+        """(alpha (M, K), mu (M, K, D), Sigma_inv (M, K, D, D), Sigma_det (M, K)) as the reference returns them
+        (:90-143).  An inspection helper in plain torch ops, in params' dtype and on its device."""
+        D, K, T = self.D, self.K, self.D * (self.D + 1) // 2
+        M = params.shape[0]
+        alpha = torch.softmax(params[:, :K], dim=1)
+        mu = params[:, K:K + K * D].reshape(M, K, D)
+        raw = params[:, K + K * D:K + K * D + K * T].reshape(M, K, T)
+        inds = torch.triu_indices(D, D, device=params.device)
+        diag = torch.arange(D, device=params.device)
+        U = torch.zeros((M, K, D, D), dtype=params.dtype, device=params.device)
+        U[:, :, inds[0], inds[1]] = raw
+        u_diag = U[:, :, diag, diag]
+        U_exp = torch.exp(u_diag)
+        log_det = -2.0 * u_diag
+        if self._has_bounds():
+            b = self._bounds().to(device=params.device, dtype=params.dtype)
+            m, c = (b[1] - b[0]) / 2.0, (b[1] + b[0]) / 2.0
+            mu = m * torch.tanh(mu) + c
+            U_exp = U_exp / torch.sqrt(m)
+            Sigma_det = torch.prod(m * torch.exp(log_det), dim=2)
+        else:
+            Sigma_det = torch.prod(torch.exp(log_det), dim=2)
+        U = U.clone()
+        U[:, :, diag, diag] = U_exp
+        Sigma_inv = torch.matmul(U.transpose(3, 2), U)
+        if numpy:
+            alpha = alpha.detach().cpu().numpy()
+            alpha = alpha / np.sum(alpha, axis=1)[:, None]
+            mu = mu.detach().cpu().numpy()
+            Sigma_inv = Sigma_inv.detach().cpu().numpy()
+        return alpha, mu, Sigma_inv, Sigma_det
+
+    def _params_or_own(self, params):
+        if params is None:
+            if self.conditioner:
+                raise ValueError("MoG built with conditioner=True needs params.")
+            return self.params
+        return params
+
+    def log_prob(self, z, params=None):
+        """density_estimator.py:172-213: z (M_z, N, D), params (M_p, D_params), M_z and M_p in {1, M} -> (M, N)."""
+        return ops.mog_log_prob(z, self._params_or_own(params), self.D, self.K, self._device_bounds())
+
+    def forward(self, params, N=100):
+        """density_estimator.py:145-170: (z (M, N, D), log_q (M, N)), float32, on params' device."""
+        M = params.size(0)
+        u = np.random.uniform(0.0, 1.0, (M, N))
+        e1 = np.random.normal(0.0, 1.0, (M, N, self.D))
+        e2 = np.random.normal(0.0, 1.0, (M, N, self.D))
+        return self._forward_from(torch.as_tensor(u, dtype=torch.float32), torch.as_tensor(e1, dtype=torch.float32),
+                                  torch.as_tensor(e2, dtype=torch.float32), params)
+
+    def _forward_from(self, u, e1, e2, params):
+        """The sampling map on injected draws: u (M, N) uniform, e1, e2 (M, N, D) standard normal."""
+        z, log_q = ops.mog_sample_raw(params.detach(), u, e1, e2, self.D, self.K, self._device_bounds())
+        home = params.device
+        return (z if z.device == home else z.to(home)), (log_q if log_q.device == home else log_q.to(home))
+
+    def sample(self, N=100, params=None, generator=None):
+        """Extension: like `__call__`, with the draws from the device RNG (`generator`: a torch.Generator of the HIP
+        device).  Not reproducible against np.random.seed."""
+        params = self._params_or_own(params)
+        dev = _lib.require_device()
+        M = params.size(0)
+        u = torch.rand((M, N), device=dev, dtype=torch.float32, generator=generator)
+        e = torch.randn((2, M, N, self.D), device=dev, dtype=torch.float32, generator=generator)
+        return self._forward_from(u, e[0], e[1], params)
+
+    def log_prob_np(self, z, params):
+        """density_estimator.py:215-233 on the host in float64 numpy, without scipy: log(sum_k alpha_k N(z; mu_k,
+        Sigma_k) + EPS).  Its only EPS is the one inside the log, so it equals `log_prob` wherever the density is well
+        above EPS and differs from it near the floor."""
+        z = np.asarray(z.detach().cpu().numpy() if torch.is_tensor(z) else z, dtype=np.float64)
+        p = params.detach().cpu().double() if torch.is_tensor(params) else torch.as_tensor(np.asarray(params)).double()
+        alpha, mu, Sigma_inv, _ = self._get_MoG_params(p, numpy=True)
+        d = z[:, :, None, :] - mu[:, None, :, :]
+        q = np.einsum("mnki,mkij,mnkj->mnk", d, Sigma_inv, d)
+        _, logdet = np.linalg.slogdet(Sigma_inv)  # log det Sigma_inv = -log det Sigma
+        log_n = -0.5 * q + 0.5 * logdet[:, None, :] - 0.5 * self.D * np.log(2.0 * np.pi)
+        return np.log(np.sum(alpha[:, None, :] * np.exp(log_n), axis=2) + MOG_EPS)

@@ -1303,3 +1303,9 @@ def ar_flow_forward_raw(omega, params, masks, bn_mean, bn_alpha, D, L, U, interv
                                       _ptr(interval_consts), z.data_ptr(), sld.data_ptr(), Mz, Mp, N, D, L, U, pstride,
                                       ws, ws_bytes, _lib.stream_ptr()))
     return z, sld  # on the compute device: the caller carries on there
+
+
+# ---------------------------------------------------------------------------
+# Mixture of Gaussians: the wrappers live in mog_ops.py (a family and a marshalling test of its own)
+# ---------------------------------------------------------------------------
+from .mog_ops import _MogLogProbFn, mog_log_prob, mog_log_prob_raw, mog_num_params, mog_sample_raw  # noqa: E402,F401
