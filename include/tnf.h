@@ -301,7 +301,12 @@ int tnf_cond_flow_forward_f32(const float* omega, const float* h, const float* W
  * saves, in `acts` (tnf_cond_flow_acts_floats(M, D, S, L) floats), the activations the backward needs.
  * tnf_cond_flow_log_prob_bwd_f32: from g_log_prob (M) to the gradients of param_net's last Linear --
  * g_W (D_params, ldgw), g_b (D_params), both overwritten -- and of its input, g_h (M, ldgh); g_z (M, D)
- * optional (NULL).  `deltas` is scratch of tnf_cond_flow_deltas_floats(M, D, S, L, H) floats; the workspace
+ * optional (NULL).  Leading dimensions beyond H (ldh, ldw, ldgh multiples of 4): the surplus columns of h and W are
+ * never read.  g_h: the first H columns of every row are overwritten, the other ldgh - H are left alone.  g_W: the
+ * call first zeroes D_params * ldgw consecutive floats from g_W on -- every column of every row, the surplus ones
+ * included and left zero, so the last row must be ldgw floats long too -- and then accumulates into the first H
+ * columns.  g_z, when given, is overwritten.  None of them needs initialising.
+ * `deltas` is scratch of tnf_cond_flow_deltas_floats(M, D, S, L, H) floats; the workspace
  * needs tnf_cond_flow_bwd_workspace_bytes.  Neither params (M, D_params) nor their gradient is ever
  * materialised (torch autograd through the reference would hold both: 2 x 82 KB per context at D = 64). */
 int64_t tnf_cond_flow_acts_floats(int64_t M, int32_t D, int32_t num_stages, int32_t num_layers);

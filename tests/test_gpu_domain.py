@@ -13,7 +13,6 @@ whole-flow limit, the layer backward above the reversible one -- the move is an 
 Tolerances are the suite's existing bars for the same quantities (tests/test_gpu_parity.py, tests/test_gpu_grad.py,
 tests/test_gpu_cond.py); none is new."""
 import contextlib
-import copy
 import math
 
 import numpy as np
@@ -21,18 +20,13 @@ import pytest
 import torch
 
 from conftest import grad_err
+from domain_helpers import (BAR_P, BAR_Z, FORWARD_FAMILIES, INV_TOL, LOGP_TOL, LQ_TOL, SLDF_TOL, ZF_TOL, _cde, _net64,
+                            _stats64_of, counts, float64, launched)
 from torch_nf_amd import _lib as L_
 
 pytestmark = pytest.mark.gpu
 
 lib = L_.lib
-
-LOGP_TOL = dict(rtol=1e-5, atol=1e-5)   # LOGP_RTOL of test_gpu_parity.py
-INV_TOL = dict(rtol=1e-4, atol=1e-4)    # z0 and sum_log_det: test_full_size_properties
-ZF_TOL = dict(rtol=2e-5, atol=1e-5)     # z of the sampling direction: test_oracle_forward_many_contexts
-LQ_TOL = dict(rtol=1e-5, atol=2e-5)     # log_q: test_oracle_forward_many_contexts
-SLDF_TOL = dict(rtol=1e-4, atol=1e-4)   # forward sum_log_det: test_full_size_properties
-BAR_P, BAR_Z = 5e-5, 5e-6               # test_flow_level_training_pair (4 x the measured reversible-pair errors)
 
 FAMILY_NAMES = {
     L_.DIAG_BWD_LAYER_FP32: "coupling_bwd_mfma", L_.DIAG_BWD_LAYER_F16: "coupling_bwd_f16",
@@ -42,8 +36,6 @@ FAMILY_NAMES = {
     L_.DIAG_FLOW_F16: "flow_fused_f16", L_.DIAG_FLOW_FP32: "flow_fused", L_.DIAG_FLOW_RANGE2: "flow_range2",
     L_.DIAG_FLOW_RANGE2_FWD: "flow_range2_fwd", L_.DIAG_COUPLING_MFMA: "coupling_mfma", L_.DIAG_COND_FLOW: "cond_flow",
 }
-FORWARD_FAMILIES = (L_.DIAG_FLOW_FUSED2, L_.DIAG_FLOW_FUSED2_FWD, L_.DIAG_FLOW_FUSED3, L_.DIAG_FLOW_F16, L_.DIAG_FLOW_FP32,
-                    L_.DIAG_FLOW_RANGE2, L_.DIAG_FLOW_RANGE2_FWD, L_.DIAG_COUPLING_MFMA)
 
 
 # ---- the domain, from the library's predicates --------------------------------------------------------------------
@@ -143,17 +135,6 @@ def tnf():
 
 
 @contextlib.contextmanager
-def float64():
-    """Run the oracle in double precision: its intermediate buffers follow torch's default dtype."""
-    before = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        yield
-    finally:
-        torch.set_default_dtype(before)
-
-
-@contextlib.contextmanager
 def variants(flow=10, layer=10):
     L_.check(lib.tnf_set_option(L_.OPT_FLOW_VARIANT, flow))
     L_.check(lib.tnf_set_option(L_.OPT_LAYER_VARIANT, layer))
@@ -162,17 +143,6 @@ def variants(flow=10, layer=10):
     finally:
         L_.check(lib.tnf_set_option(L_.OPT_FLOW_VARIANT, 10))
         L_.check(lib.tnf_set_option(L_.OPT_LAYER_VARIANT, 10))
-
-
-def counts():
-    torch.cuda.synchronize()
-    return [lib.tnf_diag_launch_count(f) for f in range(L_.DIAG_FAMILIES)]
-
-
-def launched(before, families=None):
-    """{family: launches since `before`} (only the families that moved, restricted to `families` when given)."""
-    after = counts()
-    return {f: a - b for f, (a, b) in enumerate(zip(after, before)) if a != b and (families is None or f in families)}
 
 
 def flow_inputs(D, S, L, U, Mz, Mp, N, seed):
@@ -335,28 +305,6 @@ def test_domain_training(tnf, oracle, D, L, S, Mp):
 # ---- D. conditional flow ------------------------------------------------------------------------------------------
 COND_CASES = [pytest.param(D, L, H, S, id="D%d-L%d-H%d-S%d-cond_flow" % (D, L, H, S))
               for D in (32, 64) for L in (4, 5) for H in (32, 64, 128) for S in (1, 5)]
-
-
-def _cde(tnf, D, S, L, H, seed, Dx=8, U=15):
-    torch.manual_seed(seed)
-    nf = tnf.NormFlow(D, True, "coupling", S, L, U)
-    cde = tnf.ConditionalDensityEstimator(nf, Dx, [H])
-    g = torch.Generator().manual_seed(seed)
-    for b in nf._bn_layers():
-        b.set_last_stats(torch.randn(D, generator=g) * 0.1, torch.rand(D, generator=g) * 0.5 + 0.75)
-    with torch.no_grad():
-        for p in cde.param_net.parameters():
-            p.mul_(0.5)
-    cde.cuda()
-    return nf, cde
-
-
-def _net64(cde):
-    return copy.deepcopy(cde.param_net).cpu().double()
-
-
-def _stats64_of(nf):
-    return [(b.get_last_mean().cpu().double(), b.get_last_alpha().cpu().double()) for b in nf._bn_layers()]
 
 
 @pytest.mark.parametrize("D,L,H,S", COND_CASES)
