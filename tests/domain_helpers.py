@@ -1,6 +1,7 @@
-"""What the domain sweeps share (tests/test_gpu_domain.py, tests/test_gpu_cond_domain.py): the float64 context of the
-oracle, the launch counters, the conditional-estimator input scheme and the suite's existing bars.  A helper like
-tests/mog_restatement.py: no test in here."""
+"""What the domain sweeps share (tests/test_gpu_domain.py, tests/test_gpu_cond_domain.py,
+tests/test_gpu_support_domain.py): the float64 context of the oracle, the kernel-variant switch, the launch counters, the
+conditional-estimator input scheme and the suite's existing bars.  A helper like tests/mog_restatement.py: no test in
+here."""
 import contextlib
 import copy
 
@@ -30,6 +31,18 @@ def float64():
         yield
     finally:
         torch.set_default_dtype(before)
+
+
+@contextlib.contextmanager
+def variants(flow=10, layer=10):
+    """Select the whole-flow and per-layer kernel variants for the block; the defaults (10, 10) come back afterwards."""
+    L_.check(lib.tnf_set_option(L_.OPT_FLOW_VARIANT, flow))
+    L_.check(lib.tnf_set_option(L_.OPT_LAYER_VARIANT, layer))
+    try:
+        yield
+    finally:
+        L_.check(lib.tnf_set_option(L_.OPT_FLOW_VARIANT, 10))
+        L_.check(lib.tnf_set_option(L_.OPT_LAYER_VARIANT, 10))
 
 
 def counts():

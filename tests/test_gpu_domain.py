@@ -12,7 +12,6 @@ whole-flow limit, the layer backward above the reversible one -- the move is an 
 
 Tolerances are the suite's existing bars for the same quantities (tests/test_gpu_parity.py, tests/test_gpu_grad.py,
 tests/test_gpu_cond.py); none is new."""
-import contextlib
 import math
 
 import numpy as np
@@ -21,7 +20,7 @@ import torch
 
 from conftest import grad_err
 from domain_helpers import (BAR_P, BAR_Z, FORWARD_FAMILIES, INV_TOL, LOGP_TOL, LQ_TOL, SLDF_TOL, ZF_TOL, _cde, _net64,
-                            _stats64_of, counts, float64, launched)
+                            _stats64_of, counts, float64, launched, variants)
 from torch_nf_amd import _lib as L_
 
 pytestmark = pytest.mark.gpu
@@ -132,17 +131,6 @@ def tnf():
 
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     return torch_nf_amd
-
-
-@contextlib.contextmanager
-def variants(flow=10, layer=10):
-    L_.check(lib.tnf_set_option(L_.OPT_FLOW_VARIANT, flow))
-    L_.check(lib.tnf_set_option(L_.OPT_LAYER_VARIANT, layer))
-    try:
-        yield
-    finally:
-        L_.check(lib.tnf_set_option(L_.OPT_FLOW_VARIANT, 10))
-        L_.check(lib.tnf_set_option(L_.OPT_LAYER_VARIANT, 10))
 
 
 def flow_inputs(D, S, L, U, Mz, Mp, N, seed):

@@ -17,6 +17,9 @@ __device__ __forceinline__ T logsigmoid_t(T x) { return (x < 0 ? x : (T)0) - Mth
 template <typename T>
 __device__ __forceinline__ T sigmoid_t(T x) { return (T)1 / ((T)1 + Mth<T>::exp(-x)); }
 
+__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
 // consts rows (float, D each): 0 tanh_flg, 1 softplus_flg, 2 tanh_m, 3 tanh_c, 4 softplus_m, 5 softplus_c,
 // 6 log(tanh_m) as the reference rounds it (float32 log of the float32 tanh_m)
 enum { IV_TF = 0, IV_SF, IV_TM, IV_TC, IV_SM, IV_SC, IV_LTM, IV_ROWS };
@@ -26,6 +29,10 @@ enum { IV_TF = 0, IV_SF, IV_TM, IV_TC, IV_SM, IV_SC, IV_LTM, IV_ROWS };
 template <typename T, bool INV, bool GRAD>
 __device__ __forceinline__ void interval_elem(T x, const float* __restrict__ c, int D, int d, T& out, T& ld, T& dout,
                                               T& dld) {
+    // one rounding per operation, as the reference evaluates it: contracted into an fma, 1 - t * t differs from the
+    // reference's by up to an ulp of t * t, which log(1 - t^2 + eps) amplifies by 1 / (1 - t^2) where tanh saturates
+    // (float64, |z| = 10: 2e-9 in the log-det against a 1e-11 bar)
+#pragma clang fp contract(off)
     const T eps = (T)TNF_IV_EPS;
     out = x;
     ld = 0;
@@ -44,8 +51,11 @@ __device__ __forceinline__ void interval_elem(T x, const float* __restrict__ c, 
         ld = ltm + Mth<T>::log(omt + eps);
         out = INV ? zi : tm * t + tc;
         if (GRAD) {
-            const T dl = (T)-2 * t * omt / (omt + eps);
-            dout = INV ? dzi : tm * omt;
+            // d tanh = 1 - t^2 with ONE rounding (torch's tanh backward on the host contracts it too); the log-det's
+            // own 1 - t^2, above, keeps the forward's two roundings in the denominator
+            const T dt = fma_t(-t, t, (T)1);
+            const T dl = (T)-2 * t * dt / (omt + eps);
+            dout = INV ? dzi : tm * dt;
             dld = dl * dzi;
         }
     } else if (c[IV_SF * D + d] != 0.0f) {
@@ -91,9 +101,11 @@ to_interval_kernel(const T* __restrict__ z, const float* __restrict__ consts, T*
     }
     __syncthreads();
     for (int i = tid; i < nr; i += 256) {
-        T acc = 0;
-        for (int d = 0; d < D; ++d) acc += lds[i * (D + 1) + d];
-        log_det[r0 + i] = acc;
+        // one thread sums a row serially: in double, or a float32 row of thousands of terms drifts past the float32
+        // reference's own (pairwise-summed) noise -- D = 16383: 2.3e-6 of the log-det against 5e-7
+        double acc = 0;
+        for (int d = 0; d < D; ++d) acc += (double)lds[i * (D + 1) + d];
+        log_det[r0 + i] = (T)acc;
     }
 }
 
@@ -182,14 +194,15 @@ to_simplex_kernel(const T* __restrict__ z, T* __restrict__ z_out, T* __restrict_
     }
     __syncthreads();
     for (int i = tid; i < nr; i += 256) {
-        T S = 0, sz = 0;
+        double Sd = 0, szd = 0;  // serial row sums in double (see to_interval_kernel)
         for (int d = 0; d < Din; ++d) {
             const T v = ex[i * W + d];
             const T e = Mth<T>::exp(v);
             ex[i * W + d] = e;
-            S += e;
-            sz += v;
+            Sd += (double)e;
+            szd += (double)v;
         }
+        const T S = (T)Sd, sz = (T)szd;
         const T den = S + (T)1;
         log_det[r0 + i] = Mth<T>::log((T)1 - S / den + (T)TNF_SX_EPS) - (T)Dc * Mth<T>::log(den) + sz;
         ex[i * W + Din] = den;
@@ -226,13 +239,14 @@ to_simplex_backward_kernel(const T* __restrict__ z, const T* __restrict__ g_zout
     for (int idx = tid; idx < nr * W; idx += 256) gg[idx] = gt[idx];
     __syncthreads();
     for (int i = tid; i < nr; i += 256) {
-        T S = 0, dot = 0;
+        double Sd = 0, dotd = 0;  // serial row sums in double: Din = 8190 in float32 put the gradient 2.2e-6 off
         for (int d = 0; d < Din; ++d) {
-            S += ex[i * W + d];
-            dot += gg[i * W + d] * ex[i * W + d];
+            Sd += (double)ex[i * W + d];
+            dotd += (double)gg[i * W + d] * (double)ex[i * W + d];
         }
+        const T S = (T)Sd;
         const T den = S + (T)1;
-        dot = (dot + gg[i * W + Din]) / den;
+        T dot = (T)(dotd + (double)gg[i * W + Din]) / den;
         ex[i * W + Din] = den;
         gg[i * W + Din] = dot;
         rr[i] = S / den;
