@@ -5,7 +5,7 @@
 // forward pass) and reduces the parameter gradient over the samples with float atomics
 // (one atomic per parameter per workgroup; summation order, hence the last bits, can
 // differ from run to run).  Shape- and dtype-generic like generic_kernels.hip.
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -230,10 +230,10 @@ backward_reduce_kernel(const T* __restrict__ partials, T* __restrict__ g_params,
 int launch_backward_reduce(int dtype, const void* partials, void* g_params, int64_t rows, int G, int64_t P,
                            int64_t gpstride, hipStream_t st) {
     const dim3 grid = grid_xm((P + 255) / 256, rows);
-    if (dtype == TNF_F32)
-        hipLaunchKernelGGL(backward_reduce_kernel<float>, grid, dim3(256), 0, st, (const float*)partials, (float*)g_params, rows, G, P, gpstride);
-    else
-        hipLaunchKernelGGL(backward_reduce_kernel<double>, grid, dim3(256), 0, st, (const double*)partials, (double*)g_params, rows, G, P, gpstride);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(backward_reduce_kernel<T>, grid, dim3(256), 0, st, (const T*)partials, (T*)g_params, rows, G, P, gpstride);
+    });
     return check_launch("backward_reduce");
 }
 
@@ -306,20 +306,14 @@ int launch_coupling_backward(int dtype, const void* z, const void* params, const
         tiles = G;
     }
     const dim3 grid = grid_xm(tiles, M);
-    if (dtype == TNF_F32) {
-        auto k = coupling_backward_kernel<float>;
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, (const float*)z, (const float*)params,
-                           (const float*)g_zout, (const float*)g_ld, (float*)g_z, (float*)g_params, M, Mp, N, D,
-                           L, U, upper, inverse, pstride, gpstride, (int)TS, W, (float*)partials, prow);
-    } else {
-        auto k = coupling_backward_kernel<double>;
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, (const double*)z, (const double*)params,
-                           (const double*)g_zout, (const double*)g_ld, (double*)g_z, (double*)g_params, M, Mp,
-                           N, D, L, U, upper, inverse, pstride, gpstride, (int)TS, W, (double*)partials, prow);
-    }
-    const int rc = check_launch("coupling_backward");
+    int rc = dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_lds("coupling_backward", coupling_backward_kernel<T>, grid, dim3(256), smem, st, (const T*)z,
+                          (const T*)params, (const T*)g_zout, (const T*)g_ld, (T*)g_z, (T*)g_params, M, Mp, N, D, L, U, upper,
+                          inverse, pstride, gpstride, (int)TS, W, (T*)partials, prow);
+    });
+    if (rc != TNF_OK) return rc;
+    rc = check_launch("coupling_backward");
     if (rc || !partials) return rc;
     return launch_backward_reduce(dtype, partials, g_params, rows, G, prow, gpstride, st);
 }
@@ -401,21 +395,15 @@ int launch_affine_backward(int dtype, const void* z, const void* params, const v
     if (blocks < 1) blocks = 1;
     const int64_t rpb = (N + blocks - 1) / blocks;
     const dim3 grid = grid_xm(blocks, M);
-    if (dtype == TNF_F32) {
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
         if (N > 0)
-            hipLaunchKernelGGL(affine_backward_kernel<float>, grid, dim3(256), 0, st, (const float*)z,
-                               (const float*)params, (const float*)g_zout, (const float*)g_ld, (float*)g_z,
-                               (float*)g_params, M, Mp, N, D, inverse, pstride, gpstride, rpb);
-        hipLaunchKernelGGL(affine_backward_ld_kernel<float>, dim3((unsigned)Mp), dim3(256), 0, st,
-                           (const float*)g_ld, (float*)g_params, D, gpstride);
-    } else {
-        if (N > 0)
-            hipLaunchKernelGGL(affine_backward_kernel<double>, grid, dim3(256), 0, st, (const double*)z,
-                               (const double*)params, (const double*)g_zout, (const double*)g_ld,
-                               (double*)g_z, (double*)g_params, M, Mp, N, D, inverse, pstride, gpstride, rpb);
-        hipLaunchKernelGGL(affine_backward_ld_kernel<double>, dim3((unsigned)Mp), dim3(256), 0, st,
-                           (const double*)g_ld, (double*)g_params, D, gpstride);
-    }
+            hipLaunchKernelGGL(affine_backward_kernel<T>, grid, dim3(256), 0, st, (const T*)z, (const T*)params,
+                               (const T*)g_zout, (const T*)g_ld, (T*)g_z, (T*)g_params, M, Mp, N, D, inverse, pstride,
+                               gpstride, rpb);
+        hipLaunchKernelGGL(affine_backward_ld_kernel<T>, dim3((unsigned)Mp), dim3(256), 0, st, (const T*)g_ld,
+                           (T*)g_params, D, gpstride);
+    });
     return check_launch("affine_backward");
 }
 
@@ -437,14 +425,12 @@ int launch_bn_apply_backward(int dtype, const void* g_zout, const float* alpha, 
     const int64_t total = rows * D;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (total > 0) {
-        if (dtype == TNF_F32)
-            hipLaunchKernelGGL(bn_apply_backward_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st,
-                               (const float*)g_zout, alpha, (float*)g_z, D, inverse, total);
-        else
-            hipLaunchKernelGGL(bn_apply_backward_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st,
-                               (const double*)g_zout, alpha, (double*)g_z, D, inverse, total);
-    }
+    if (total > 0)
+        dispatch_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(bn_apply_backward_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)g_zout, alpha,
+                               (T*)g_z, D, inverse, total);
+        });
     return check_launch("bn_apply_backward");
 }
 

@@ -22,6 +22,7 @@
 // workgroup's waves).  Each wave owns 16*BT contexts; the matrix pipe is the binding unit
 // (2 * H * D_params * 3 f16 flops per context), everything else rides under it.
 #include "cond_tile.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -479,15 +480,13 @@ static int launch_cond_variant(const CondArgs& a, hipStream_t st) {
     typedef TileStream<KS * 128 + 4, kCondG<KS>, NW, kCondNS<KS, BT, NW>> Stream;
     constexpr int D = 16 * DT;
     const size_t smem = (size_t)Stream::LDS_U4 * 16 + (size_t)NW * 16 * BT * (D + 4 + 40) * 4;
-    auto k = cond_flow_kernel<DT, KS, BT, NW, SAVE, FWD>;
-    if (smem > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     const int64_t per_wg = (int64_t)NW * 16 * BT;
     const int64_t blocks = (a.M + per_wg - 1) / per_wg;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "cond_flow: grid too large");
     diag_count(TNF_DIAG_COND_FLOW);
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * NW), smem, st, a);
-    return check_launch("cond_flow");
+    const int rc = launch_lds("cond_flow", cond_flow_kernel<DT, KS, BT, NW, SAVE, FWD>, dim3((unsigned)blocks), dim3(64 * NW),
+                              smem, st, a);
+    return rc != TNF_OK ? rc : check_launch("cond_flow");
 }
 
 thread_local int g_cond_variant = 0;  // testing hook: 0 = by M, 1 = (BT 1, 4 waves), 2 = (BT 1, 8 waves), 3 = (BT 2, 8 waves)

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "cond_tile.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -1055,14 +1056,11 @@ template <int DT, int KS, int BT, int NW>
 static int launch_gh(const CondBwdArgs& a, hipStream_t st) {
     typedef TileStream<KS * 256, 4 / KS, NW, 4> TStream;
     const size_t smem = (size_t)TStream::LDS_U4 * 16;
-    auto k = cond_gh_kernel<DT, KS, BT, NW>;
-    if (smem > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     const int64_t per_wg = (int64_t)NW * 16 * BT;
     const int64_t blocks = (a.M + per_wg - 1) / per_wg;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "cond_gh: grid too large");
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * NW), smem, st, a);
-    return check_launch("cond_gh");
+    const int rc = launch_lds("cond_gh", cond_gh_kernel<DT, KS, BT, NW>, dim3((unsigned)blocks), dim3(64 * NW), smem, st, a);
+    return rc != TNF_OK ? rc : check_launch("cond_gh");
 }
 
 template <int DT, int KS, int BT, int NW, bool GH>
@@ -1071,14 +1069,11 @@ static int launch_bwd_variant(const CondBwdArgs& a, hipStream_t st) {
     typedef TileStream<KS * 256, 4 / KS, NW, 2> TStream;
     constexpr int D = 16 * DT;
     const size_t smem = (size_t)(PStream::LDS_U4 + (GH ? TStream::LDS_U4 : 0)) * 16 + (size_t)NW * 16 * BT * (D + 4) * 4;
-    auto k = cond_flow_bwd_kernel<DT, KS, BT, NW, GH>;
-    if (smem > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     const int64_t per_wg = (int64_t)NW * 16 * BT;
     const int64_t blocks = (a.M + per_wg - 1) / per_wg;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "cond_flow_bwd: grid too large");
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * NW), smem, st, a);
-    return check_launch("cond_flow_bwd");
+    const int rc = launch_lds("cond_flow_bwd", cond_flow_bwd_kernel<DT, KS, BT, NW, GH>, dim3((unsigned)blocks), dim3(64 * NW), smem, st, a);
+    return rc != TNF_OK ? rc : check_launch("cond_flow_bwd");
 }
 
 template <int DT, int KS>

@@ -18,7 +18,7 @@
 //
 // tanh'(a) = 1 - h^2 = 4 r (1 - r) with r the folded sigmoid the forward pass produces.
 #include "mfma_tile.h"
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -493,12 +493,6 @@ coupling_bwd_mfma_kernel(BwdArgs a) {
     }
 }
 
-template <int H, int L>
-static void launch_bwd_hl(const BwdArgs& a, int inverse, dim3 grid, hipStream_t st) {
-    if (inverse) hipLaunchKernelGGL((coupling_bwd_mfma_kernel<H, L, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((coupling_bwd_mfma_kernel<H, L, false>), grid, dim3(256), 0, st, a);
-}
-
 int launch_coupling_backward_mfma(const float* z, const float* params, const float* g_zout,
                                   const float* g_ld, float* g_z, float* g_params, int64_t M, int64_t Mp,
                                   int64_t N, int D, int L, int U, int upper, int inverse, int64_t pstride,
@@ -513,20 +507,13 @@ int launch_coupling_backward_mfma_args(const BwdArgs& a, int D, int L, int inver
     const int64_t M = a.M, N = a.N;
     diag_count(TNF_DIAG_BWD_LAYER_FP32);
     const int64_t ntiles = (N + 15) / 16;
-    int64_t bx = (ntiles + 3) / 4;
-    int64_t cap = 512 / M;  // persistent grid (2 workgroups per CU): each ends with one atomic per parameter
-    if (cap < 1) cap = 1;
-    if (bx > cap) bx = cap;
-    const dim3 grid = grid_xm(bx, M);
-    if (D == 64) {
-        if (L == 1) launch_bwd_hl<32, 1>(a, inverse, grid, st);
-        else if (L == 2) launch_bwd_hl<32, 2>(a, inverse, grid, st);
-        else launch_bwd_hl<32, 3>(a, inverse, grid, st);
-    } else {
-        if (L == 1) launch_bwd_hl<16, 1>(a, inverse, grid, st);
-        else if (L == 2) launch_bwd_hl<16, 2>(a, inverse, grid, st);
-        else launch_bwd_hl<16, 3>(a, inverse, grid, st);
-    }
+    // persistent grid (2 workgroups per CU): each ends with one atomic per parameter
+    const dim3 grid = grid_xm(persistent_bx(ntiles, 4, 512, M), M);
+    dispatch_hl(D, L, [&](auto h, auto l) {
+        dispatch_bool(inverse, [&](auto inv) {
+            hipLaunchKernelGGL((coupling_bwd_mfma_kernel<h(), l(), inv()>), grid, dim3(256), 0, st, a);
+        });
+    });
     return check_launch("coupling_backward_mfma");
 }
 

@@ -6,7 +6,7 @@
 #include <cstring>
 #include "flow_layer.h"
 #include "mfma_tile.h"
-#include "tnf_common.h"
+#include "launch.h"
 
 #ifndef TNF_LAYER_NTSTORE
 #define TNF_LAYER_NTSTORE 0
@@ -161,14 +161,10 @@ int launch_flow_images(const float* params, float* images, int64_t Mp, int D, in
                        hipStream_t st) {
     const dim3 grid = grid_xm(2 * S, Mp);
     const int64_t fl = mfma_image_floats(D, L);
-#define TNF_IMG(HH, LL) \
-    hipLaunchKernelGGL((flow_images_kernel<HH, LL>), grid, dim3(64), 0, st, params, images, S, U, pstride, fl, Mp, g_launch_gate)
-    if (D == 64) {
-        if (L == 1) TNF_IMG(32, 1); else if (L == 2) TNF_IMG(32, 2); else TNF_IMG(32, 3);
-    } else {
-        if (L == 1) TNF_IMG(16, 1); else if (L == 2) TNF_IMG(16, 2); else TNF_IMG(16, 3);
-    }
-#undef TNF_IMG
+    dispatch_hl(D, L, [&](auto h, auto l) {
+        hipLaunchKernelGGL((flow_images_kernel<h(), l()>), grid, dim3(64), 0, st, params, images, S, U, pstride, fl, Mp,
+                           g_launch_gate);
+    });
     return check_launch("flow_images");
 }
 
@@ -412,30 +408,8 @@ static void launch_k(const MfmaLayerArgs& a, int64_t M, hipStream_t st) {
                            0, st, b);
         return;
     }
-    int64_t bx = (ngroups + 3) / 4;
-    int64_t cap = 2048 / M;
-    if (cap < 1) cap = 1;
-    if (bx > cap) bx = cap;
-    hipLaunchKernelGGL((coupling_mfma_kernel<H, L, INV, NT, LDSOP>), grid_xm(bx, M), dim3(256),
-                       0, st, a);
-}
-
-template <int H, int L, bool INV>
-static void launch_v(const MfmaLayerArgs& a, int64_t M, hipStream_t st) {
-    const int v = (a.image && g_layer_variant < 10) ? g_layer_variant : 0;  // the LDS variants need the prepared image
-    if (L == 2 && v == 1) launch_k<H, L, INV, 2, true>(a, M, st);
-    else if (L == 2 && v == 2) launch_k<H, L, INV, 1, true>(a, M, st);
-    else if (L == 2 && v == 3) launch_k<H, L, INV, 1, false>(a, M, st);
-    else launch_k<H, L, INV, 2, false>(a, M, st);
-}
-
-template <int H>
-static void launch_h(const MfmaLayerArgs& a, int64_t M, hipStream_t st) {
-    switch (a.L) {
-        case 1: a.inverse ? launch_v<H, 1, true>(a, M, st) : launch_v<H, 1, false>(a, M, st); break;
-        case 2: a.inverse ? launch_v<H, 2, true>(a, M, st) : launch_v<H, 2, false>(a, M, st); break;
-        default: a.inverse ? launch_v<H, 3, true>(a, M, st) : launch_v<H, 3, false>(a, M, st); break;
-    }
+    hipLaunchKernelGGL((coupling_mfma_kernel<H, L, INV, NT, LDSOP>), grid_xm(persistent_bx(ngroups, 4, 2048, M), M),
+                       dim3(256), 0, st, a);
 }
 
 int launch_coupling_mfma(const MfmaLayerArgs& a, hipStream_t st) {
@@ -444,8 +418,15 @@ int launch_coupling_mfma(const MfmaLayerArgs& a, hipStream_t st) {
     const int64_t M = a.Mz > a.Mp ? a.Mz : a.Mp;
     if (a.N <= 0) return TNF_OK;
     diag_count(TNF_DIAG_COUPLING_MFMA);
-    if (a.D == 64) launch_h<32>(a, M, st);
-    else launch_h<16>(a, M, st);
+    const int v = (a.image && g_layer_variant < 10) ? g_layer_variant : 0;  // the LDS variants need the prepared image
+    dispatch_hl(a.D, a.L, [&](auto h, auto l) {
+        dispatch_bool(a.inverse, [&](auto inv) {
+            if (l() == 2 && v == 1) launch_k<h(), l(), inv(), 2, true>(a, M, st);
+            else if (l() == 2 && v == 2) launch_k<h(), l(), inv(), 1, true>(a, M, st);
+            else if (l() == 2 && v == 3) launch_k<h(), l(), inv(), 1, false>(a, M, st);
+            else launch_k<h(), l(), inv(), 2, false>(a, M, st);
+        });
+    });
     return check_launch("coupling_mfma");
 }
 
@@ -901,8 +882,9 @@ int launch_flow_forward_train_bwd(const float* omega, const float* params, const
     rc = launch_gmax(g_sld, M * N, gmaxw, st);
     if (rc) return rc;
     const float* v_last = states + (int64_t)(nl - 1) * plane;
-    hipLaunchKernelGGL(fold_sums_kernel, grid_xm(sb, M), dim3(256), (size_t)fs_rpi * 2 * D * sizeof(float), st, g_z, v_last,
-                       g_sld, PQ, Ssum, Mp, N, D, rpb);
+    rc = launch_lds("flow_forward_train_bwd", fold_sums_kernel, grid_xm(sb, M), dim3(256),
+                    (size_t)fs_rpi * 2 * D * sizeof(float), st, g_z, v_last, g_sld, PQ, Ssum, Mp, N, D, rpb);
+    if (rc) return rc;
     int cur = 0;
     for (int c = nl - 1; c >= 0; --c) {
         // fold behind layer c: PQ holds its sums (from fold_sums for the last one, else from the layer c+1 backward)

@@ -13,6 +13,7 @@
 // One 16-sample tile per wave iteration; per tile and layer 4*(HT*UT + (L-1)*UT*UT + HT*UT) * 2
 // MFMAs.  This is the coverage path for shapes without a narrow specialisation: HBM-bound for
 // small U, fp32-pipe-bound for U >= 32.
+#include "launch.h"
 #include "wide_tile.h"
 
 namespace tnf {
@@ -229,32 +230,6 @@ int launch_wide_images(const float* params, float* images, int64_t Mp, int D, in
     return check_launch("wide_images");
 }
 
-template <int HT, int UT>
-static int launch_wide_hu(const MfmaLayerArgs& a, const WideLayout& wl, dim3 grid, size_t smem, hipStream_t st) {
-    if (a.inverse) {
-        auto k = coupling_wide_kernel<HT, UT, true>;
-        if (smem > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail(TNF_ELAUNCH, "coupling_wide: cannot reserve %zu B of LDS", smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a, wl);
-    } else {
-        auto k = coupling_wide_kernel<HT, UT, false>;
-        if (smem > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail(TNF_ELAUNCH, "coupling_wide: cannot reserve %zu B of LDS", smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a, wl);
-    }
-    return TNF_OK;
-}
-
-template <int HT>
-static int launch_wide_h(const MfmaLayerArgs& a, const WideLayout& wl, dim3 grid, size_t smem, hipStream_t st) {
-    switch (wl.UT) {
-        case 1: return launch_wide_hu<HT, 1>(a, wl, grid, smem, st);
-        case 2: return launch_wide_hu<HT, 2>(a, wl, grid, smem, st);
-        case 3: return launch_wide_hu<HT, 3>(a, wl, grid, smem, st);
-        default: return launch_wide_hu<HT, 4>(a, wl, grid, smem, st);
-    }
-}
-
 int launch_coupling_wide(const MfmaLayerArgs& a, hipStream_t st) {
     if (!wide_supported(a.D, a.L, a.U))
         return fail(TNF_EUNSUPPORTED, "coupling_wide: no kernel for D=%d L=%d U=%d", a.D, a.L, a.U);
@@ -263,18 +238,14 @@ int launch_coupling_wide(const MfmaLayerArgs& a, hipStream_t st) {
     const WideLayout wl = wide_layout(a.D, a.L, a.U);
     const size_t smem = (size_t)(4 * 128 + wl.floats()) * sizeof(float);
     const int64_t ntiles = (a.N + 15) / 16;
-    int64_t bx = (ntiles + 3) / 4;
-    int64_t cap = 1024 / M;
-    if (cap < 1) cap = 1;
-    if (bx > cap) bx = cap;
-    const dim3 grid = grid_xm(bx, M);
-    int rc;
-    switch (wl.HT) {
-        case 1: rc = launch_wide_h<1>(a, wl, grid, smem, st); break;
-        case 2: rc = launch_wide_h<2>(a, wl, grid, smem, st); break;
-        case 3: rc = launch_wide_h<3>(a, wl, grid, smem, st); break;
-        default: rc = launch_wide_h<4>(a, wl, grid, smem, st); break;
-    }
+    const dim3 grid = grid_xm(persistent_bx(ntiles, 4, 1024, M), M);
+    const int rc = dispatch_1to4(wl.HT, [&](auto ht) {
+        return dispatch_1to4(wl.UT, [&](auto ut) {
+            return dispatch_bool(a.inverse, [&](auto inv) {
+                return launch_lds("coupling_wide", coupling_wide_kernel<ht(), ut(), inv()>, grid, dim3(256), smem, st, a, wl);
+            });
+        });
+    });
     if (rc != TNF_OK) return rc;
     return check_launch("coupling_wide");
 }

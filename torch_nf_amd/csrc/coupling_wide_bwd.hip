@@ -23,6 +23,7 @@
 //
 // Records cost 4 (3 HT + 4 L UT) KB per 16 samples (2.4 KB per sample at D = 64, U = 64, L = 2): written once, read once,
 // chunked to 2^18 samples so that the workspace stays below 1 GB whatever N is.
+#include "launch.h"
 #include "maf_tile.h"
 #include "wide_tile.h"
 
@@ -448,40 +449,6 @@ int64_t wide_bwd_workspace(int64_t N, int D, int L, int U) {
     return rec + wide_bwd_chunks(N) * kWideBwdSlices * P * 4;
 }
 
-template <int HT, int UT, int L>
-static int launch_wide_bwd_t(const WideBwdArgs& a, const WideGwArgs& g, const WideLayout& wl, const WideBwdLayout& bl,
-                             size_t smem, hipStream_t st) {
-    auto k = coupling_wide_bwd_kernel<HT, UT, L>;
-    if (smem > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return fail(TNF_ELAUNCH, "coupling_wide_bwd: cannot reserve %zu B of LDS", smem);
-    const int64_t ntiles = (a.n1 - a.n0 + 15) / 16;
-    int64_t bx = (ntiles + 3) / 4;
-    if (bx > 512) bx = 512;
-    hipLaunchKernelGGL(k, dim3((unsigned)bx), dim3(256), smem, st, a, wl, bl, g.rc);
-    hipLaunchKernelGGL((wide_gw_kernel<HT, UT>), dim3((unsigned)(2 * (L + 1) * g.G)), dim3(256), 0, st, g);
-    return TNF_OK;
-}
-
-template <int HT, int UT>
-static int launch_wide_bwd_l(const WideBwdArgs& a, const WideGwArgs& g, const WideLayout& wl, const WideBwdLayout& bl,
-                             size_t smem, hipStream_t st) {
-    if (wl.L == 1) return launch_wide_bwd_t<HT, UT, 1>(a, g, wl, bl, smem, st);
-    if (wl.L == 2) return launch_wide_bwd_t<HT, UT, 2>(a, g, wl, bl, smem, st);
-    if constexpr (UT <= 2) return launch_wide_bwd_t<HT, UT, 3>(a, g, wl, bl, smem, st);
-    return fail(TNF_EUNSUPPORTED, "coupling_wide_bwd: num_layers=%d with %d unit tiles", wl.L, UT);
-}
-
-template <int HT>
-static int launch_wide_bwd_u(const WideBwdArgs& a, const WideGwArgs& g, const WideLayout& wl, const WideBwdLayout& bl,
-                             size_t smem, hipStream_t st) {
-    switch (wl.UT) {
-        case 1: return launch_wide_bwd_l<HT, 1>(a, g, wl, bl, smem, st);
-        case 2: return launch_wide_bwd_l<HT, 2>(a, g, wl, bl, smem, st);
-        case 3: return launch_wide_bwd_l<HT, 3>(a, g, wl, bl, smem, st);
-        default: return launch_wide_bwd_l<HT, 4>(a, g, wl, bl, smem, st);
-    }
-}
-
 // One shared parameter row (M_p = 1); N = all samples of the call (M batches of one row are one batch).
 // g_params accumulates (the caller zeroed it).  ws: wide_bwd_workspace(N, D, L, U) bytes.
 int launch_coupling_backward_wide(const float* z, const float* params, const float* g_zout, const float* g_ld, float* g_z,
@@ -504,13 +471,22 @@ int launch_coupling_backward_wide(const float* z, const float* params, const flo
         WideBwdArgs a{z, params, g_zout, g_ld, g_z, rec, partials + ci * kWideBwdSlices * P, N, ci * kWideBwdChunk,
                       (ci + 1) * kWideBwdChunk < N ? (ci + 1) * kWideBwdChunk : N, D, U, upper, inverse};
         WideGwArgs g{rec, a.partials, (a.n1 - a.n0 + 15) / 16, D / 2, U, L, (int)P, kWideBwdSlices, rc, nullptr};
-        int rcode;
-        switch (wl.HT) {
-            case 1: rcode = launch_wide_bwd_u<1>(a, g, wl, bl, smem, st); break;
-            case 2: rcode = launch_wide_bwd_u<2>(a, g, wl, bl, smem, st); break;
-            case 3: rcode = launch_wide_bwd_u<3>(a, g, wl, bl, smem, st); break;
-            default: rcode = launch_wide_bwd_u<4>(a, g, wl, bl, smem, st); break;
-        }
+        const int64_t bx = persistent_bx(g.ntiles, 4, 512, 1);
+        const int rcode = dispatch_1to4(wl.HT, [&](auto ht) {
+            return dispatch_1to4(wl.UT, [&](auto ut) {
+                auto go = [&](auto l) {
+                    const int r = launch_lds("coupling_wide_bwd", coupling_wide_bwd_kernel<ht(), ut(), l()>, dim3((unsigned)bx),
+                                             dim3(256), smem, st, a, wl, bl, g.rc);
+                    if (r != TNF_OK) return r;
+                    hipLaunchKernelGGL((wide_gw_kernel<ht(), ut()>), dim3((unsigned)(2 * (l() + 1) * g.G)), dim3(256), 0, st, g);
+                    return (int)TNF_OK;
+                };
+                if (wl.L == 1) return go(int_c<1>{});
+                if (wl.L == 2) return go(int_c<2>{});
+                if constexpr (ut() <= 2) return go(int_c<3>{});
+                return fail(TNF_EUNSUPPORTED, "coupling_wide_bwd: num_layers=%d with %d unit tiles", wl.L, ut());
+            });
+        });
         if (rcode != TNF_OK) return rcode;
     }
     const int rcode = check_launch("coupling_wide_bwd");
@@ -788,38 +764,6 @@ int64_t maf_wide_bwd_workspace(int64_t N, int D, int L, int U) {
            wide_bwd_chunks(N) * kWideBwdSlices * maf_num_params_(D, L, U) * 4;
 }
 
-template <int DT, int UT, int L>
-static int launch_maf_wide_t(const MafWideBwdArgs& a, const WideGwArgs& g, const MafLayout& wl, const WideBwdLayout& bl,
-                             size_t smem, hipStream_t st) {
-    auto k = maf_wide_bwd_kernel<DT, UT, L>;
-    if (smem > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return fail(TNF_ELAUNCH, "maf_wide_bwd: cannot reserve %zu B of LDS", smem);
-    const int64_t ntiles = (a.n1 - a.n0 + 15) / 16;
-    int64_t bx = (ntiles + 3) / 4;
-    if (bx > 512) bx = 512;
-    hipLaunchKernelGGL(k, dim3((unsigned)bx), dim3(256), smem, st, a, wl, bl, g.rc);
-    hipLaunchKernelGGL((wide_gw_kernel<DT, UT>), dim3((unsigned)(2 * (L + 1) * g.G)), dim3(256), 0, st, g);
-    return TNF_OK;
-}
-template <int DT, int UT>
-static int launch_maf_wide_l(const MafWideBwdArgs& a, const WideGwArgs& g, const MafLayout& wl, const WideBwdLayout& bl,
-                             size_t smem, hipStream_t st) {
-    if (wl.L == 1) return launch_maf_wide_t<DT, UT, 1>(a, g, wl, bl, smem, st);
-    if (wl.L == 2) return launch_maf_wide_t<DT, UT, 2>(a, g, wl, bl, smem, st);
-    if constexpr (UT <= 2) return launch_maf_wide_t<DT, UT, 3>(a, g, wl, bl, smem, st);
-    return fail(TNF_EUNSUPPORTED, "maf_wide_bwd: num_layers=%d with %d unit tiles", wl.L, UT);
-}
-template <int DT>
-static int launch_maf_wide_u(const MafWideBwdArgs& a, const WideGwArgs& g, const MafLayout& wl, const WideBwdLayout& bl,
-                             size_t smem, hipStream_t st) {
-    switch (wl.UT) {
-        case 1: return launch_maf_wide_l<DT, 1>(a, g, wl, bl, smem, st);
-        case 2: return launch_maf_wide_l<DT, 2>(a, g, wl, bl, smem, st);
-        case 3: return launch_maf_wide_l<DT, 3>(a, g, wl, bl, smem, st);
-        default: return launch_maf_wide_l<DT, 4>(a, g, wl, bl, smem, st);
-    }
-}
-
 int launch_maf_backward_wide(const float* z, const float* params, const float* masks, const float* g_zout, const float* g_ld,
                              float* g_z, float* g_params, int64_t N, int D, int L, int U, int64_t gpstride, void* ws,
                              hipStream_t st) {
@@ -843,13 +787,22 @@ int launch_maf_backward_wide(const float* z, const float* params, const float* m
         MafWideBwdArgs a{z, params, masks, timg, g_zout, g_ld, g_z, rec, ci * kWideBwdChunk,
                          (ci + 1) * kWideBwdChunk < N ? (ci + 1) * kWideBwdChunk : N, D, U};
         WideGwArgs g{rec, part, (a.n1 - a.n0 + 15) / 16, D, U, L, (int)P, kWideBwdSlices, rc, masks};
-        int rcode;
-        switch (wl.DT) {
-            case 1: rcode = launch_maf_wide_u<1>(a, g, wl, bl, smem, st); break;
-            case 2: rcode = launch_maf_wide_u<2>(a, g, wl, bl, smem, st); break;
-            case 3: rcode = launch_maf_wide_u<3>(a, g, wl, bl, smem, st); break;
-            default: rcode = launch_maf_wide_u<4>(a, g, wl, bl, smem, st); break;
-        }
+        const int64_t bx = persistent_bx(g.ntiles, 4, 512, 1);
+        const int rcode = dispatch_1to4(wl.DT, [&](auto dt) {
+            return dispatch_1to4(wl.UT, [&](auto ut) {
+                auto go = [&](auto l) {
+                    const int r = launch_lds("maf_wide_bwd", maf_wide_bwd_kernel<dt(), ut(), l()>, dim3((unsigned)bx), dim3(256),
+                                             smem, st, a, wl, bl, g.rc);
+                    if (r != TNF_OK) return r;
+                    hipLaunchKernelGGL((wide_gw_kernel<dt(), ut()>), dim3((unsigned)(2 * (l() + 1) * g.G)), dim3(256), 0, st, g);
+                    return (int)TNF_OK;
+                };
+                if (wl.L == 1) return go(int_c<1>{});
+                if (wl.L == 2) return go(int_c<2>{});
+                if constexpr (ut() <= 2) return go(int_c<3>{});
+                return fail(TNF_EUNSUPPORTED, "maf_wide_bwd: num_layers=%d with %d unit tiles", wl.L, ut());
+            });
+        });
         if (rcode != TNF_OK) return rcode;
     }
     const int rcode = check_launch("maf_wide_bwd");

@@ -12,7 +12,7 @@
 //   generic kernels (double, or D > 64): one sample per lane, run-time loops, eta and z through the vector caches.
 // g_eta = sum_n g[n] T(z[n]) is a parameter gradient and is reduced in a fixed order: every workgroup owns one partial
 // row in the workspace, every entry of it is owned by one thread, and an ordered pass adds the rows (no float atomics).
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -397,15 +397,11 @@ int64_t ef_dot_bwd_workspace(int family, int64_t M, int64_t N, int D) {
     return M * G * Deta * 8;
 }
 
-template <typename T, int FAM>
-static void ef_launch_suff(const void* z, void* out, int64_t rows, int D, int Deta, unsigned blocks, hipStream_t st) {
-    hipLaunchKernelGGL((ef_suffstats_kernel<T, FAM>), dim3(blocks), dim3(256), 0, st, (const T*)z, (T*)out, rows, D, Deta);
-}
-template <typename T, int FAM>
-static void ef_launch_suff_bwd(const void* z, const void* g_T, void* g_z, int64_t rows, int D, int Deta, unsigned blocks,
-                               hipStream_t st) {
-    hipLaunchKernelGGL((ef_suffstats_backward_kernel<T, FAM>), dim3(blocks), dim3(256), 0, st, (const T*)z, (const T*)g_T,
-                       (T*)g_z, rows, D, Deta);
+// (dtype, family) -> <T, FAM> of the dtype-generic kernels: f(T{}, int_c<FAM>{})
+template <class F> static auto dispatch_ef(int dtype, int family, F&& f) {
+    return dispatch_dtype(dtype, [&](auto t) {
+        return family == TNF_EF_MVN ? f(t, int_c<TNF_EF_MVN>{}) : f(t, int_c<TNF_EF_DIRICHLET>{});
+    });
 }
 
 int launch_ef_suffstats(int dtype, int family, const void* z, void* out, int64_t rows, int D, hipStream_t st) {
@@ -413,14 +409,11 @@ int launch_ef_suffstats(int dtype, int family, const void* z, void* out, int64_t
     const int Deta = (int)ef_num_eta(family, D);
     const int64_t blocks = (rows * Deta + 255) / 256;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "ef_suffstats: grid too large");
-    const unsigned b = (unsigned)blocks;
-    if (dtype == TNF_F32) {
-        if (family == TNF_EF_MVN) ef_launch_suff<float, TNF_EF_MVN>(z, out, rows, D, Deta, b, st);
-        else ef_launch_suff<float, TNF_EF_DIRICHLET>(z, out, rows, D, Deta, b, st);
-    } else {
-        if (family == TNF_EF_MVN) ef_launch_suff<double, TNF_EF_MVN>(z, out, rows, D, Deta, b, st);
-        else ef_launch_suff<double, TNF_EF_DIRICHLET>(z, out, rows, D, Deta, b, st);
-    }
+    dispatch_ef(dtype, family, [&](auto t, auto fam) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((ef_suffstats_kernel<T, fam()>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)z, (T*)out,
+                           rows, D, Deta);
+    });
     return check_launch("ef_suffstats");
 }
 
@@ -430,14 +423,11 @@ int launch_ef_suffstats_backward(int dtype, int family, const void* z, const voi
     const int Deta = (int)ef_num_eta(family, D);
     const int64_t blocks = (rows * D + 255) / 256;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "ef_suffstats_backward: grid too large");
-    const unsigned b = (unsigned)blocks;
-    if (dtype == TNF_F32) {
-        if (family == TNF_EF_MVN) ef_launch_suff_bwd<float, TNF_EF_MVN>(z, g_T, g_z, rows, D, Deta, b, st);
-        else ef_launch_suff_bwd<float, TNF_EF_DIRICHLET>(z, g_T, g_z, rows, D, Deta, b, st);
-    } else {
-        if (family == TNF_EF_MVN) ef_launch_suff_bwd<double, TNF_EF_MVN>(z, g_T, g_z, rows, D, Deta, b, st);
-        else ef_launch_suff_bwd<double, TNF_EF_DIRICHLET>(z, g_T, g_z, rows, D, Deta, b, st);
-    }
+    dispatch_ef(dtype, family, [&](auto t, auto fam) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((ef_suffstats_backward_kernel<T, fam()>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)z,
+                           (const T*)g_T, (T*)g_z, rows, D, Deta);
+    });
     return check_launch("ef_suffstats_backward");
 }
 
@@ -473,19 +463,6 @@ static int ef_tiles_per_wg(int64_t M, int64_t N, int64_t* bx) {
             return fail(TNF_EUNSUPPORTED, "ef_dot: no fused kernel for D=%d", D);                                 \
     }
 
-template <typename T, int FAM>
-static void ef_launch_dot_generic(const void* z, const void* eta, void* out, int64_t M, int64_t N, int D, int64_t ld_eta,
-                                  hipStream_t st) {
-    hipLaunchKernelGGL((ef_dot_generic_kernel<T, FAM>), grid_xm((N + 255) / 256, M), dim3(256), 0, st, (const T*)z,
-                       (const T*)eta, (T*)out, M, N, D, ld_eta);
-}
-template <typename T, int FAM>
-static void ef_launch_gz_generic(const void* z, const void* eta, const void* g, void* g_z, int64_t M, int64_t N, int D,
-                                 int64_t ld_eta, hipStream_t st) {
-    hipLaunchKernelGGL((ef_dot_generic_gz_kernel<T, FAM>), grid_xm((N * D + 255) / 256, M), dim3(256), 0, st, (const T*)z,
-                       (const T*)eta, (const T*)g, (T*)g_z, M, N, D, ld_eta);
-}
-
 int launch_ef_dot(int dtype, int family, const void* z, const void* eta, void* out, int64_t M, int64_t N, int D,
                   int64_t ld_eta, hipStream_t st) {
     if (M == 0 || N == 0) return 0;
@@ -503,13 +480,11 @@ int launch_ef_dot(int dtype, int family, const void* z, const void* eta, void* o
         ef_count(TNF_EF_COUNT_DOT);
         return check_launch("ef_dot");
     }
-    if (dtype == TNF_F32) {
-        if (family == TNF_EF_MVN) ef_launch_dot_generic<float, TNF_EF_MVN>(z, eta, out, M, N, D, ld_eta, st);
-        else ef_launch_dot_generic<float, TNF_EF_DIRICHLET>(z, eta, out, M, N, D, ld_eta, st);
-    } else {
-        if (family == TNF_EF_MVN) ef_launch_dot_generic<double, TNF_EF_MVN>(z, eta, out, M, N, D, ld_eta, st);
-        else ef_launch_dot_generic<double, TNF_EF_DIRICHLET>(z, eta, out, M, N, D, ld_eta, st);
-    }
+    dispatch_ef(dtype, family, [&](auto t, auto fam) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((ef_dot_generic_kernel<T, fam()>), grid_xm((N + 255) / 256, M), dim3(256), 0, st, (const T*)z,
+                           (const T*)eta, (T*)out, M, N, D, ld_eta);
+    });
     return check_launch("ef_dot (generic)");
 }
 
@@ -521,9 +496,10 @@ static int ef_launch_geta(const void* z, const void* g, void* g_eta, int64_t M, 
     const int64_t ntiles = (N + R - 1) / R;
     const int64_t per = ntiles > 0 ? (ntiles + G - 1) / G : 1;
     const size_t smem = ((size_t)R * D + R) * sizeof(T);
-    hipLaunchKernelGGL((ef_geta_partial_kernel<T, FAM>), grid_xm(G, M), dim3(EF_GETA_THREADS), smem, st, (const T*)z,
-                       (const T*)g, (T*)ws, M, N, D, Deta, G, R, per);
-    int rc = check_launch("ef_dot_backward (g_eta partials)");
+    int rc = launch_lds("ef_dot_backward", ef_geta_partial_kernel<T, FAM>, grid_xm(G, M), dim3(EF_GETA_THREADS), smem, st,
+                        (const T*)z, (const T*)g, (T*)ws, M, N, D, Deta, G, R, per);
+    if (rc) return rc;
+    rc = check_launch("ef_dot_backward (g_eta partials)");
     if (rc) return rc;
     hipLaunchKernelGGL((ef_geta_reduce_kernel<T>), dim3((unsigned)((M * Deta + 255) / 256)), dim3(256), 0, st,
                        (const T*)ws, (T*)g_eta, M, Deta, G);
@@ -548,24 +524,21 @@ int launch_ef_dot_backward(int dtype, int family, const void* z, const void* eta
                                    (const float*)z, (const float*)eta, (const float*)g_out, (float*)g_z, M, N, D, ld_eta);
             }
             ef_count(TNF_EF_COUNT_DOT_BWD);
-        } else if (dtype == TNF_F32) {
-            if (family == TNF_EF_MVN) ef_launch_gz_generic<float, TNF_EF_MVN>(z, eta, g_out, g_z, M, N, D, ld_eta, st);
-            else ef_launch_gz_generic<float, TNF_EF_DIRICHLET>(z, eta, g_out, g_z, M, N, D, ld_eta, st);
         } else {
-            if (family == TNF_EF_MVN) ef_launch_gz_generic<double, TNF_EF_MVN>(z, eta, g_out, g_z, M, N, D, ld_eta, st);
-            else ef_launch_gz_generic<double, TNF_EF_DIRICHLET>(z, eta, g_out, g_z, M, N, D, ld_eta, st);
+            dispatch_ef(dtype, family, [&](auto t, auto fam) {
+                using T = decltype(t);
+                hipLaunchKernelGGL((ef_dot_generic_gz_kernel<T, fam()>), grid_xm((N * D + 255) / 256, M), dim3(256), 0, st,
+                                   (const T*)z, (const T*)eta, (const T*)g_out, (T*)g_z, M, N, D, ld_eta);
+            });
         }
         const int rc = check_launch("ef_dot_backward (g_z)");
         if (rc) return rc;
     }
     if (g_eta) {
         if ((M * Deta + 255) / 256 > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "ef_dot_backward: grid too large");
-        if (dtype == TNF_F32) {
-            if (family == TNF_EF_MVN) return ef_launch_geta<float, TNF_EF_MVN>(z, g_out, g_eta, M, N, D, Deta, ws, st);
-            return ef_launch_geta<float, TNF_EF_DIRICHLET>(z, g_out, g_eta, M, N, D, Deta, ws, st);
-        }
-        if (family == TNF_EF_MVN) return ef_launch_geta<double, TNF_EF_MVN>(z, g_out, g_eta, M, N, D, Deta, ws, st);
-        return ef_launch_geta<double, TNF_EF_DIRICHLET>(z, g_out, g_eta, M, N, D, Deta, ws, st);
+        return dispatch_ef(dtype, family, [&](auto t, auto fam) {
+            return ef_launch_geta<decltype(t), fam()>(z, g_out, g_eta, M, N, D, Deta, ws, st);
+        });
     }
     return TNF_OK;
 }

@@ -24,7 +24,7 @@
 // ~21 KB, built once per call by flow_rev_images_kernel) is prefetched into registers during a
 // step and committed to the other half of a two-slot LDS ring at its end, one barrier per step.
 #include "f16_tile.h"
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -1156,18 +1156,6 @@ coupling_bwd_f16_kernel(BwdArgs a) {
     }
 }
 
-template <int H, int L>
-static void launch_layer_f16(const BwdArgs& a, int inverse, dim3 grid, hipStream_t st) {
-    const dim3 blk(kLayerNW * 64);
-    if (inverse) {
-        if (a.U <= 15) hipLaunchKernelGGL((coupling_bwd_f16_kernel<H, L, true, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((coupling_bwd_f16_kernel<H, L, false, true>), grid, blk, 0, st, a);
-    } else {
-        if (a.U <= 15) hipLaunchKernelGGL((coupling_bwd_f16_kernel<H, L, true, false>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((coupling_bwd_f16_kernel<H, L, false, false>), grid, blk, 0, st, a);
-    }
-}
-
 // shapes of mfma_supported(); g_ld and g_z required; g_z_out may be NULL only when g_lp seeds the layer (finalize)
 int launch_coupling_backward_f16(const BwdArgs& a, int D, int L, int inverse, hipStream_t st) {
     if (!(D == 64 || D == 32) || L < 1 || L > 3 || a.U < 1 || a.U > 16)
@@ -1175,19 +1163,14 @@ int launch_coupling_backward_f16(const BwdArgs& a, int D, int L, int inverse, hi
     if (a.N <= 0) return TNF_OK;
     diag_count(TNF_DIAG_BWD_LAYER_F16);
     const int64_t ntiles = (a.N + 15) / 16;
-    int64_t bx = (ntiles + kLayerNW - 1) / kLayerNW;
-    int64_t cap = (256 + a.M - 1) / a.M;
-    if (bx > cap) bx = cap;
-    const dim3 grid = grid_xm(bx, a.M);
-    if (D == 64) {
-        if (L == 1) launch_layer_f16<32, 1>(a, inverse, grid, st);
-        else if (L == 2) launch_layer_f16<32, 2>(a, inverse, grid, st);
-        else launch_layer_f16<32, 3>(a, inverse, grid, st);
-    } else {
-        if (L == 1) launch_layer_f16<16, 1>(a, inverse, grid, st);
-        else if (L == 2) launch_layer_f16<16, 2>(a, inverse, grid, st);
-        else launch_layer_f16<16, 3>(a, inverse, grid, st);
-    }
+    const dim3 grid = grid_xm(persistent_bx_ceil(ntiles, kLayerNW, 256, a.M), a.M);
+    dispatch_hl(D, L, [&](auto h, auto l) {
+        dispatch_bool(a.U <= 15, [&](auto spare) {
+            dispatch_bool(inverse, [&](auto inv) {
+                hipLaunchKernelGGL((coupling_bwd_f16_kernel<h(), l(), spare(), inv()>), grid, dim3(kLayerNW * 64), 0, st, a);
+            });
+        });
+    });
     return check_launch("coupling_backward_f16");
 }
 
@@ -1235,9 +1218,8 @@ static bool rev_use_pair(int D, int S, int L, int U) {
 static int64_t rev_blocks_x(int64_t M, int64_t N, bool pair) {
     const int64_t units = pair ? (N + 16 * kPairNT - 1) / (16 * kPairNT) : (N + 15) / 16;  // groups of kPairNT tiles / tiles
     const int nw = pair ? kPairNW : kRevNW;
-    int64_t bx = (units + nw - 1) / nw;
-    const int64_t cap = (256 + M - 1) / M;
-    return bx > cap ? cap : (bx < 1 ? 1 : bx);
+    const int64_t bx = persistent_bx_ceil(units, nw, 256, M);
+    return bx < 1 ? 1 : bx;
 }
 // workspace: [rimg | g_fold (Mp, 2S, 2, D) + glp_sum (Mp) + gmax (1) + overflow (1) | glp partials | partial rows];
 // g_fold .. overflow are zeroed by the backward
@@ -1308,20 +1290,15 @@ static int launch_rev(const float* z0, const float* params, const float* bn_mean
                   reinterpret_cast<int*>(ws + w.part), reinterpret_cast<float*>(ws + w.glpp), overflow};
     // the partial rows are indexed by this launch's own grid; the reduction reads as many
     const int64_t nred = (Mp == 1 ? M : 1) * bx;
-    if (pair) {
-        const size_t smem = (size_t)pair_lds_bytes(D, S, L);
-        auto kern = U <= 15 ? flow_bwd_pair_kernel<H, L, true> : flow_bwd_pair_kernel<H, L, false>;
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail(TNF_ELAUNCH, "flow_bwd_pair: cannot reserve %zu B of LDS", smem);
-        hipLaunchKernelGGL(kern, grid_xm(bx, M), dim3(kPairNW * 64), smem, st, a);
-    } else {
-        const size_t smem = (size_t)rev_lds_bytes(D, S, L, U);
-        auto kern = U <= 15 ? flow_bwd_f16_kernel<H, L, kRevNW, true> : flow_bwd_f16_kernel<H, L, kRevNW, false>;
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail(TNF_ELAUNCH, "flow_bwd_f16: cannot reserve %zu B of LDS", smem);
-        hipLaunchKernelGGL(kern, grid_xm(bx, M), dim3(kRevNW * 64), smem, st, a);
-    }
-    int rc = check_launch("flow_bwd_f16");
+    int rc = dispatch_bool(U <= 15, [&](auto spare) {
+        if (pair)
+            return launch_lds("flow_bwd_pair", flow_bwd_pair_kernel<H, L, spare()>, grid_xm(bx, M), dim3(kPairNW * 64),
+                              (size_t)pair_lds_bytes(D, S, L), st, a);
+        return launch_lds("flow_bwd_f16", flow_bwd_f16_kernel<H, L, kRevNW, spare()>, grid_xm(bx, M), dim3(kRevNW * 64),
+                          (size_t)rev_lds_bytes(D, S, L, U), st, a);
+    });
+    if (rc) return rc;
+    rc = check_launch("flow_bwd_f16");
     if (rc) return rc;
     {
         const int H_ = D / 2;
@@ -1349,18 +1326,10 @@ int launch_flow_bwd_rev(const float* z0, const float* params, const float* bn_me
         M = 1;
     }
     char* wsb = reinterpret_cast<char*>(ws);
-#define TNF_REV(HH, LL) \
-    return launch_rev<HH, LL>(z0, params, bn_mean, bn_alpha, g_lp, g_z, g_params, M, Mp, N, S, U, pstride, gpstride, wsb, \
-                              overflow_out, st)
-    if (D == 64) {
-        if (L == 1) TNF_REV(32, 1);
-        if (L == 2) TNF_REV(32, 2);
-        TNF_REV(32, 3);
-    }
-    if (L == 1) TNF_REV(16, 1);
-    if (L == 2) TNF_REV(16, 2);
-    TNF_REV(16, 3);
-#undef TNF_REV
+    return dispatch_hl(D, L, [&](auto h, auto l) {
+        return launch_rev<h(), l()>(z0, params, bn_mean, bn_alpha, g_lp, g_z, g_params, M, Mp, N, S, U, pstride, gpstride, wsb,
+                                    overflow_out, st);
+    });
 }
 
 }  // namespace tnf

@@ -8,8 +8,8 @@
 #ifndef TNF_STAMP
 #define TNF_STAMP 0
 #endif
+#include "launch.h"
 #include "mfma_tile.h"
-#include "tnf_common.h"
 
 namespace tnf {
 
@@ -228,38 +228,9 @@ bool flow_fused_supported(int D, int S, int L, int U) {
 template <int H, int L, bool INV, int NT, int NW>
 static int launch_t(const FlowFusedArgs& a, int64_t M, hipStream_t st) {
     const size_t smem = flow_lds_bytes<H, L>(a.S);
-    auto kern = flow_fused_kernel<H, L, INV, NT, NW>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return fail(TNF_ELAUNCH, "flow_fused: cannot reserve %zu B of LDS", smem);
-    const int64_t ngroups = (a.N + 16 * NT - 1) / (16 * NT);
-    int64_t bx = (ngroups + NW - 1) / NW;
-    int64_t cap = (256 + M - 1) / M;  // one workgroup per CU (LDS-limited), persistent over its groups
-    if (bx > cap) bx = cap;
-    hipLaunchKernelGGL(kern, grid_xm(bx, M), dim3(NW * 64), smem, st, a);
-    return TNF_OK;
-}
-
-template <int H, int L, bool INV>
-static int launch_v(const FlowFusedArgs& a, int64_t M, hipStream_t st) {
-    if (L == 2) {
-        switch (g_flow_variant) {
-            case 1: return launch_t<H, L, INV, 1, 8>(a, M, st);
-            case 2: return launch_t<H, L, INV, 1, 12>(a, M, st);
-            case 3: return launch_t<H, L, INV, 1, 16>(a, M, st);
-            case 4: return launch_t<H, L, INV, 2, 12>(a, M, st);
-            default: break;
-        }
-    }
-    return launch_t<H, L, INV, 2, 8>(a, M, st);
-}
-
-template <int H>
-static int launch_h(const FlowFusedArgs& a, int L, int inverse, int64_t M, hipStream_t st) {
-    switch (L) {
-        case 1: return inverse ? launch_v<H, 1, true>(a, M, st) : launch_v<H, 1, false>(a, M, st);
-        case 2: return inverse ? launch_v<H, 2, true>(a, M, st) : launch_v<H, 2, false>(a, M, st);
-        default: return inverse ? launch_v<H, 3, true>(a, M, st) : launch_v<H, 3, false>(a, M, st);
-    }
+    // one workgroup per CU (LDS-limited), persistent over its groups
+    const int64_t bx = persistent_bx_ceil((a.N + 16 * NT - 1) / (16 * NT), NW, 256, M);
+    return launch_lds("flow_fused", flow_fused_kernel<H, L, INV, NT, NW>, grid_xm(bx, M), dim3(NW * 64), smem, st, a);
 }
 
 int launch_flow_fused(const float* z, const float* images, const float* fold, const float* ldc,
@@ -271,7 +242,20 @@ int launch_flow_fused(const float* z, const float* images, const float* fold, co
     if (N <= 0) return TNF_OK;
     FlowFusedArgs a{z, images, fold, ldc, z_out, sum_log_det, log_prob, Mz, Mp, N, S, U};
     diag_count(TNF_DIAG_FLOW_FP32);
-    int rc = (D == 64) ? launch_h<32>(a, L, inverse, M, st) : launch_h<16>(a, L, inverse, M, st);
+    const int rc = dispatch_hl(D, L, [&](auto h, auto l) {
+        return dispatch_bool(inverse, [&](auto inv) {
+            if (l() == 2) {
+                switch (g_flow_variant) {
+                    case 1: return launch_t<h(), l(), inv(), 1, 8>(a, M, st);
+                    case 2: return launch_t<h(), l(), inv(), 1, 12>(a, M, st);
+                    case 3: return launch_t<h(), l(), inv(), 1, 16>(a, M, st);
+                    case 4: return launch_t<h(), l(), inv(), 2, 12>(a, M, st);
+                    default: break;
+                }
+            }
+            return launch_t<h(), l(), inv(), 2, 8>(a, M, st);
+        });
+    });
     if (rc != TNF_OK) return rc;
     return check_launch("flow_fused");
 }

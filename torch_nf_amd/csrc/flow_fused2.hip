@@ -6,7 +6,7 @@
 #include <type_traits>
 
 #include "f16_tile2.h"
-#include "tnf_common.h"
+#include "launch.h"
 
 // launch geometry (tuning macros; the defaults are what ships)
 #ifndef TNF2_NT
@@ -1133,8 +1133,7 @@ static size_t flow2_lds_bytes(int S) {
 }
 
 static size_t flow2_lds_bytes_rt(int D, int S, int L) {
-    if (D == 64) return L == 1 ? flow2_lds_bytes<32, 1>(S) : (L == 2 ? flow2_lds_bytes<32, 2>(S) : flow2_lds_bytes<32, 3>(S));
-    return L == 1 ? flow2_lds_bytes<16, 1>(S) : (L == 2 ? flow2_lds_bytes<16, 2>(S) : flow2_lds_bytes<16, 3>(S));
+    return dispatch_hl(D, L, [&](auto h, auto l) { return flow2_lds_bytes<h(), l()>(S); });
 }
 
 bool flow_fused2_supported(int D, int S, int L, int U) {
@@ -1150,15 +1149,9 @@ static int launch2_t(const Flow2Args& a, int64_t M, hipStream_t st) {
     const size_t stage_bytes = (size_t)NW * 16 * 2 * H * sizeof(float);
     b.stage_out = (!PAD && H == 32 && a.z_out != nullptr && smem + stage_bytes <= 160 * 1024 && TNF2_FUSED_STAGE) ? 1 : 0;
     if (b.stage_out || PAD) smem += stage_bytes;  // PAD: every row goes in and out through the staging tiles
-    auto kern = flow_fused2_kernel<H, L, NT, NW, SS, FWD, PAD>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return fail(TNF_ELAUNCH, "flow_fused2: cannot reserve %zu B of LDS", smem);
-    const int64_t ngroups = (a.N + 16 * NT - 1) / (16 * NT);
-    int64_t bx = (ngroups + NW - 1) / NW;
-    int64_t cap = (256 + M - 1) / M;  // one workgroup per CU (LDS-limited), persistent over its groups
-    if (bx > cap) bx = cap;
-    hipLaunchKernelGGL(kern, grid_xm(bx, M), dim3(NW * 64), smem, st, b);
-    return TNF_OK;
+    // one workgroup per CU (LDS-limited), persistent over its groups
+    const int64_t bx = persistent_bx_ceil((a.N + 16 * NT - 1) / (16 * NT), NW, 256, M);
+    return launch_lds("flow_fused2", flow_fused2_kernel<H, L, NT, NW, SS, FWD, PAD>, grid_xm(bx, M), dim3(NW * 64), smem, st, b);
 }
 
 template <int H, int L, bool PAD = false>
@@ -1168,9 +1161,9 @@ static int launch2_v(const Flow2Args& a, int64_t M, int forward, hipStream_t st)
     constexpr int NW = H == 16 ? TNF2_NW16 : TNF2_NW;
 #if TNF2_UNROLL
     if (a.S == 4 && (!(PAD && H == 32) || TNF2_PAD_UNROLL32))
-        return forward ? launch2_t<H, L, TNF2_NT, NW, 4, true, PAD>(a, M, st) : launch2_t<H, L, TNF2_NT, NW, 4, false, PAD>(a, M, st);
+        return dispatch_bool(forward, [&](auto fwd) { return launch2_t<H, L, TNF2_NT, NW, 4, fwd(), PAD>(a, M, st); });
 #endif
-    return forward ? launch2_t<H, L, TNF2_NT, NW, 0, true, PAD>(a, M, st) : launch2_t<H, L, TNF2_NT, NW, 0, false, PAD>(a, M, st);
+    return dispatch_bool(forward, [&](auto fwd) { return launch2_t<H, L, TNF2_NT, NW, 0, fwd(), PAD>(a, M, st); });
 }
 
 int launch_flow_fused2(const float* z, float* z0, float* sum_log_det, float* log_prob, int64_t Mz, int64_t Mp, int64_t N,
@@ -1182,13 +1175,11 @@ int launch_flow_fused2(const float* z, float* z0, float* sum_log_det, float* log
     if (N <= 0) return TNF_OK;
     const int64_t M = Mz > Mp ? Mz : Mp;
     const FlowLayout fl = flow_layout(D, S, L, U);
-    Flow2Args a{z, z0, sum_log_det, log_prob, Mz, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage,
-                fl.p_up + fl.p_low, fl.p_up, interval_consts, slow_count};
+    Flow2Args a = flow2_args(z, z0, sum_log_det, log_prob, Mz, Mp, N, S, U, params, pstride, bn_mean, bn_alpha, fl,
+                             interval_consts, slow_count);
     a.log_q = forward ? log_q : nullptr;
     diag_count(forward ? TNF_DIAG_FLOW_FUSED2_FWD : TNF_DIAG_FLOW_FUSED2);
-    int rc;
-    if (D == 64) rc = L == 1 ? launch2_v<32, 1>(a, M, forward, st) : (L == 2 ? launch2_v<32, 2>(a, M, forward, st) : launch2_v<32, 3>(a, M, forward, st));
-    else rc = L == 1 ? launch2_v<16, 1>(a, M, forward, st) : (L == 2 ? launch2_v<16, 2>(a, M, forward, st) : launch2_v<16, 3>(a, M, forward, st));
+    const int rc = dispatch_hl(D, L, [&](auto h, auto l) { return launch2_v<h(), l()>(a, M, forward, st); });
     if (rc != TNF_OK) return rc;
     return check_launch("flow_fused2");
 }
@@ -1215,18 +1206,13 @@ int launch_flow_padded(const float* z, float* z_out, float* sum_log_det, float* 
     if (N <= 0) return TNF_OK;
     const int64_t M = Mz > Mp ? Mz : Mp;
     const FlowLayout fl = flow_layout(D, S, L, U);
-    Flow2Args a{z, z_out, sum_log_det, log_prob, Mz, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage,
-                fl.p_up + fl.p_low, fl.p_up, nullptr, slow_count};
+    Flow2Args a = flow2_args(z, z_out, sum_log_det, log_prob, Mz, Mp, N, S, U, params, pstride, bn_mean, bn_alpha, fl, nullptr,
+                             slow_count);
     a.log_q = forward ? log_q : nullptr;
     a.Dr = D;
     diag_count(forward ? TNF_DIAG_FLOW_PADDED_FWD : TNF_DIAG_FLOW_PADDED);
-    int rc;
-    if (pad_half(D) == 32)
-        rc = L == 1 ? launch2_v<32, 1, true>(a, M, forward, st)
-                    : (L == 2 ? launch2_v<32, 2, true>(a, M, forward, st) : launch2_v<32, 3, true>(a, M, forward, st));
-    else
-        rc = L == 1 ? launch2_v<16, 1, true>(a, M, forward, st)
-                    : (L == 2 ? launch2_v<16, 2, true>(a, M, forward, st) : launch2_v<16, 3, true>(a, M, forward, st));
+    // D <= 31 -> H = 16, D = 33 .. 63 -> H = 32: dispatch_hl on the padded width
+    const int rc = dispatch_hl(2 * pad_half(D), L, [&](auto h, auto l) { return launch2_v<h(), l(), true>(a, M, forward, st); });
     if (rc != TNF_OK) return rc;
     return check_launch("flow_padded");
 }
@@ -1250,14 +1236,9 @@ static int launch_range_t(const Range2Args& ra_in, int64_t M, hipStream_t st) {
         kern = hf ? (hl ? flow_range2_kernel<H, L, NT, NW, true, true, PREC> : flow_range2_kernel<H, L, NT, NW, true, false, PREC>)
                   : (hl ? flow_range2_kernel<H, L, NT, NW, false, true, PREC> : flow_range2_kernel<H, L, NT, NW, false, false, PREC>);
     }
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return fail(TNF_ELAUNCH, "flow_range2: cannot reserve %zu B of LDS", smem);
-    const int64_t ngroups = (ra.f.N + 16 * NT - 1) / (16 * NT);
-    int64_t bx = (ngroups + NW - 1) / NW;
-    int64_t cap = (256 * TNF2_RANGE_WGPC + M - 1) / M;  // registers allow one 8-wave workgroup per CU
-    if (bx > cap) bx = cap;
-    hipLaunchKernelGGL(kern, grid_xm(bx, M), dim3(NW * 64), smem, st, ra);
-    return TNF_OK;
+    // registers allow one 8-wave workgroup per CU
+    const int64_t bx = persistent_bx_ceil((ra.f.N + 16 * NT - 1) / (16 * NT), NW, 256 * TNF2_RANGE_WGPC, M);
+    return launch_lds("flow_range2", kern, grid_xm(bx, M), dim3(NW * 64), smem, st, ra);
 }
 
 // the preparation launch of a chain (Range2Args::prep_out): one workgroup per (launch of the chain, context)
@@ -1265,26 +1246,37 @@ template <int H, int L, int PREC, bool FWD = false>
 static int launch_range_prep_t(const Range2Args& ra, int64_t Mp, int nlaunch, hipStream_t st) {
     constexpr int NT = TNF2_RANGE_NT, NW = TNF2_RANGE_NW;
     const size_t smem = (size_t)range2_lds_floats<H, L>(ra.per_launch) * sizeof(float);
-    auto kern = flow_range2_kernel<H, L, NT, NW, false, false, PREC, FWD>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return fail(TNF_ELAUNCH, "flow_range2 (preparation): cannot reserve %zu B of LDS", smem);
-    hipLaunchKernelGGL(kern, grid_xm(nlaunch, Mp), dim3(NW * 64), smem, st, ra);
-    return TNF_OK;
+    return launch_lds("flow_range2 (preparation)", flow_range2_kernel<H, L, NT, NW, false, false, PREC, FWD>,
+                      grid_xm(nlaunch, Mp), dim3(NW * 64), smem, st, ra);
+}
+
+// one launch of a chain: the preparation launch writes prep_out and takes no prep; the streaming launches read prep
+static Range2Args range2_args(const Flow2Args& f, int c_hi, int c_lo, const float* ld_in, int store_cond, const float* prep,
+                              float* prep_out, int per_launch, int64_t prep_slot) {
+    Range2Args ra;
+    ra.f = f;
+    ra.c_hi = c_hi;
+    ra.c_lo = c_lo;
+    ra.ld_in = ld_in;
+    ra.store_cond = store_cond;
+    ra.prep = prep;
+    ra.prep_out = prep_out;
+    ra.per_launch = per_launch;
+    ra.prep_slot = prep_slot;
+    return ra;
 }
 
 int64_t flow_chain2_prep_floats(int D, int S, int L, int per_launch) {
     // per context: one region per launch, each at the stride of a full range
     if (per_launch < 1) per_launch = 1;
     const int nlaunch = (2 * S + per_launch - 1) / per_launch;
-    const int64_t slot = (D == 64) ? (L == 1 ? range2_region_floats<32, 1>(per_launch) : (L == 2 ? range2_region_floats<32, 2>(per_launch) : range2_region_floats<32, 3>(per_launch)))
-                                   : (L == 1 ? range2_region_floats<16, 1>(per_launch) : (L == 2 ? range2_region_floats<16, 2>(per_launch) : range2_region_floats<16, 3>(per_launch)));
+    const int64_t slot = dispatch_hl(D, L, [&](auto h, auto l) { return (int64_t)range2_region_floats<h(), l()>(per_launch); });
     return nlaunch * slot;
 }
 
 bool flow_range2_supported(int D, int L, int U, int nlayers) {
     if (!mfma_supported(D, L, U) || nlayers < 1) return false;
-    const size_t b = (D == 64) ? (L == 1 ? range2_lds_floats<32, 1>(nlayers) : (L == 2 ? range2_lds_floats<32, 2>(nlayers) : range2_lds_floats<32, 3>(nlayers)))
-                               : (L == 1 ? range2_lds_floats<16, 1>(nlayers) : (L == 2 ? range2_lds_floats<16, 2>(nlayers) : range2_lds_floats<16, 3>(nlayers)));
+    const size_t b = dispatch_hl(D, L, [&](auto h, auto l) { return (size_t)range2_lds_floats<h(), l()>(nlayers); });
     return b * sizeof(float) <= 160 * 1024;
 }
 
@@ -1305,52 +1297,26 @@ int launch_flow_chain2(const float* z, float* zbuf, float* ldbuf, float* z0, flo
     const int64_t prep_slot = flow_chain2_prep_floats(D, S, L, per_launch) / nlaunch;
     if (nlaunch < 2) prep_ws = nullptr;  // one launch: its own prologue is the preparation
     if (prep_ws) {  // every launch's prologue in one small launch up front (Range2Args::prep)
-        Range2Args ra;
-        ra.f = Flow2Args{z, nullptr, nullptr, nullptr, Mp, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage,
-                         fl.p_up + fl.p_low, fl.p_up, interval_consts, nullptr};
-        ra.c_hi = nl - 1;
-        ra.c_lo = nl - per_launch > 0 ? nl - per_launch : 0;
-        ra.ld_in = nullptr;
-        ra.store_cond = 0;
-        ra.prep = nullptr;
-        ra.prep_out = prep_ws;
-        ra.per_launch = per_launch;
-        ra.prep_slot = prep_slot;
-        int rc;
-#define TNF_PREP(HH, LL) rc = prec == 1 ? launch_range_prep_t<HH, LL, 1>(ra, Mp, nlaunch, st) : launch_range_prep_t<HH, LL, 0>(ra, Mp, nlaunch, st)
-        if (D == 64) {
-            if (L == 1) TNF_PREP(32, 1); else if (L == 2) TNF_PREP(32, 2); else TNF_PREP(32, 3);
-        } else {
-            if (L == 1) TNF_PREP(16, 1); else if (L == 2) TNF_PREP(16, 2); else TNF_PREP(16, 3);
-        }
-#undef TNF_PREP
+        const Range2Args ra = range2_args(
+            flow2_args(z, nullptr, nullptr, nullptr, Mp, Mp, N, S, U, params, pstride, bn_mean, bn_alpha, fl, interval_consts, nullptr),
+            nl - 1, nl - per_launch > 0 ? nl - per_launch : 0, nullptr, 0, nullptr, prep_ws, per_launch, prep_slot);
+        const int rc = dispatch_hl(D, L, [&](auto h, auto l) {
+            return prec == 1 ? launch_range_prep_t<h(), l(), 1>(ra, Mp, nlaunch, st) : launch_range_prep_t<h(), l(), 0>(ra, Mp, nlaunch, st);
+        });
         if (rc != TNF_OK) return rc;
     }
     for (int c_hi = nl - 1; c_hi >= 0; c_hi -= per_launch) {
         const int c_lo = c_hi - per_launch + 1 > 0 ? c_hi - per_launch + 1 : 0;
         const bool first = c_hi == nl - 1, last = c_lo == 0;
-        Range2Args ra;
-        ra.f = Flow2Args{first ? z : zbuf, last ? z0 : zbuf, last ? sum_log_det : ldbuf, last ? log_prob : nullptr,
-                         first ? Mz : M, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage, fl.p_up + fl.p_low, fl.p_up,
-                         interval_consts, slow_count};
-        ra.c_hi = c_hi;
-        ra.c_lo = c_lo;
-        ra.ld_in = first ? nullptr : ldbuf;
         // the conditioner half of the range's last layer must be written unless it is in zbuf already: a later launch of
         // ONE layer did not touch it (with more layers per launch the layer before transformed it inside the launch)
-        ra.store_cond = (first || c_hi > c_lo) ? 1 : 0;
-        ra.prep = prep_ws;
-        ra.prep_out = nullptr;
-        ra.per_launch = per_launch;
-        ra.prep_slot = prep_slot;
-        int rc;
-#define TNF_RANGE(HH, LL) rc = prec == 1 ? launch_range_t<HH, LL, 1>(ra, M, st) : launch_range_t<HH, LL, 0>(ra, M, st)
-        if (D == 64) {
-            if (L == 1) TNF_RANGE(32, 1); else if (L == 2) TNF_RANGE(32, 2); else TNF_RANGE(32, 3);
-        } else {
-            if (L == 1) TNF_RANGE(16, 1); else if (L == 2) TNF_RANGE(16, 2); else TNF_RANGE(16, 3);
-        }
-#undef TNF_RANGE
+        const Range2Args ra = range2_args(
+            flow2_args(first ? z : zbuf, last ? z0 : zbuf, last ? sum_log_det : ldbuf, last ? log_prob : nullptr, first ? Mz : M,
+                       Mp, N, S, U, params, pstride, bn_mean, bn_alpha, fl, interval_consts, slow_count),
+            c_hi, c_lo, first ? nullptr : ldbuf, (first || c_hi > c_lo) ? 1 : 0, prep_ws, nullptr, per_launch, prep_slot);
+        const int rc = dispatch_hl(D, L, [&](auto h, auto l) {
+            return prec == 1 ? launch_range_t<h(), l(), 1>(ra, M, st) : launch_range_t<h(), l(), 0>(ra, M, st);
+        });
         if (rc != TNF_OK) return rc;
     }
     return check_launch("flow_chain2");
@@ -1369,46 +1335,22 @@ int launch_flow_chain2_fwd(const float* omega, float* z, float* sum_log_det, int
     const FlowLayout fl = flow_layout(D, S, L, U);
     const int64_t prep_slot = flow_chain2_prep_floats(D, S, L, 1) / nl;
     if (nl < 2) prep_ws = nullptr;
-    int rc;
-#define TNF_FWD_DISPATCH(CALL)                                                              \
-    if (D == 64) {                                                                          \
-        if (L == 1) rc = CALL(32, 1); else if (L == 2) rc = CALL(32, 2); else rc = CALL(32, 3); \
-    } else {                                                                                \
-        if (L == 1) rc = CALL(16, 1); else if (L == 2) rc = CALL(16, 2); else rc = CALL(16, 3); \
-    }
     if (prep_ws) {
-        Range2Args ra;
-        ra.f = Flow2Args{omega, nullptr, nullptr, nullptr, Mp, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage,
-                         fl.p_up + fl.p_low, fl.p_up, nullptr, nullptr};
-        ra.c_hi = ra.c_lo = 0;
-        ra.ld_in = nullptr;
-        ra.store_cond = 0;
-        ra.prep = nullptr;
-        ra.prep_out = prep_ws;
-        ra.per_launch = 1;
-        ra.prep_slot = prep_slot;
-#define TNF_FWD_PREP(HH, LL) launch_range_prep_t<HH, LL, 0, true>(ra, Mp, nl, st)
-        TNF_FWD_DISPATCH(TNF_FWD_PREP)
-#undef TNF_FWD_PREP
+        const Range2Args ra = range2_args(
+            flow2_args(omega, nullptr, nullptr, nullptr, Mp, Mp, N, S, U, params, pstride, bn_mean, bn_alpha, fl, nullptr, nullptr),
+            0, 0, nullptr, 0, nullptr, prep_ws, 1, prep_slot);
+        const int rc = dispatch_hl(D, L, [&](auto h, auto l) { return launch_range_prep_t<h(), l(), 0, true>(ra, Mp, nl, st); });
         if (rc != TNF_OK) return rc;
     }
     for (int c = 0; c < nl; ++c) {
-        Range2Args ra;
-        ra.f = Flow2Args{c == 0 ? omega : z, z, sum_log_det, nullptr, c == 0 ? Mz : M, Mp, N, S, U, params, bn_mean, bn_alpha,
-                         pstride, fl.stage, fl.p_up + fl.p_low, fl.p_up, nullptr, slow_count};
-        ra.c_hi = ra.c_lo = c;
-        ra.ld_in = c == 0 ? nullptr : sum_log_det;
-        ra.store_cond = c == 0 ? 1 : 0;  // the first launch works out of place: the conditioner half moves too
-        ra.prep = prep_ws;
-        ra.prep_out = nullptr;
-        ra.per_launch = 1;
-        ra.prep_slot = prep_slot;
-#define TNF_FWD_RANGE(HH, LL) launch_range_t<HH, LL, 0, true>(ra, M, st)
-        TNF_FWD_DISPATCH(TNF_FWD_RANGE)
-#undef TNF_FWD_RANGE
+        // the first launch works out of place: the conditioner half moves too
+        const Range2Args ra = range2_args(
+            flow2_args(c == 0 ? omega : z, z, sum_log_det, nullptr, c == 0 ? Mz : M, Mp, N, S, U, params, pstride, bn_mean,
+                       bn_alpha, fl, nullptr, slow_count),
+            c, c, c == 0 ? nullptr : sum_log_det, c == 0 ? 1 : 0, prep_ws, nullptr, 1, prep_slot);
+        const int rc = dispatch_hl(D, L, [&](auto h, auto l) { return launch_range_t<h(), l(), 0, true>(ra, M, st); });
         if (rc != TNF_OK) return rc;
     }
-#undef TNF_FWD_DISPATCH
     return check_launch("flow_chain2_fwd");
 }
 

@@ -5,7 +5,7 @@
 #include <type_traits>
 
 #include "f16_tile3.h"
-#include "tnf_common.h"
+#include "launch.h"
 
 #ifndef TNF3_NW
 #define TNF3_NW 8   // waves per workgroup (one workgroup per CU: the operand images take most of the LDS)
@@ -243,8 +243,7 @@ static size_t flow3_lds_bytes(int S) {
 }
 
 static size_t flow3_lds_bytes_rt(int D, int S, int L) {
-    if (D == 64) return L == 1 ? flow3_lds_bytes<32, 1>(S) : (L == 2 ? flow3_lds_bytes<32, 2>(S) : flow3_lds_bytes<32, 3>(S));
-    return L == 1 ? flow3_lds_bytes<16, 1>(S) : (L == 2 ? flow3_lds_bytes<16, 2>(S) : flow3_lds_bytes<16, 3>(S));
+    return dispatch_hl(D, L, [&](auto h, auto l) { return flow3_lds_bytes<h(), l()>(S); });
 }
 
 bool flow_fused3_supported(int D, int S, int L, int U) {
@@ -255,15 +254,9 @@ bool flow_fused3_supported(int D, int S, int L, int U) {
 template <int H, int L, int NW, int SS>
 static int launch3_t(const Flow2Args& a, int64_t M, hipStream_t st) {
     const size_t smem = flow3_lds_bytes<H, L>(a.S);
-    auto kern = flow_fused3_kernel<H, L, NW, SS>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return fail(TNF_ELAUNCH, "flow_fused3: cannot reserve %zu B of LDS", smem);
-    const int64_t ngroups = (a.N + 31) / 32;
-    int64_t bx = (ngroups + NW - 1) / NW;
-    int64_t cap = (256 + M - 1) / M;  // one workgroup per CU (LDS-limited), persistent over its groups
-    if (bx > cap) bx = cap;
-    hipLaunchKernelGGL(kern, grid_xm(bx, M), dim3(NW * 64), smem, st, a);
-    return TNF_OK;
+    // one workgroup per CU (LDS-limited), persistent over its groups
+    const int64_t bx = persistent_bx_ceil((a.N + 31) / 32, NW, 256, M);
+    return launch_lds("flow_fused3", flow_fused3_kernel<H, L, NW, SS>, grid_xm(bx, M), dim3(NW * 64), smem, st, a);
 }
 
 template <int H, int L>
@@ -282,12 +275,10 @@ int launch_flow_fused3(const float* z, float* z0, float* sum_log_det, float* log
     if (N <= 0) return TNF_OK;
     const int64_t M = Mz > Mp ? Mz : Mp;
     const FlowLayout fl = flow_layout(D, S, L, U);
-    Flow2Args a{z, z0, sum_log_det, log_prob, Mz, Mp, N, S, U, params, bn_mean, bn_alpha, pstride, fl.stage,
-                fl.p_up + fl.p_low, fl.p_up, interval_consts, slow_count};
+    const Flow2Args a = flow2_args(z, z0, sum_log_det, log_prob, Mz, Mp, N, S, U, params, pstride, bn_mean, bn_alpha, fl,
+                                   interval_consts, slow_count);
     diag_count(TNF_DIAG_FLOW_FUSED3);
-    int rc;
-    if (D == 64) rc = L == 1 ? launch3_v<32, 1>(a, M, st) : (L == 2 ? launch3_v<32, 2>(a, M, st) : launch3_v<32, 3>(a, M, st));
-    else rc = L == 1 ? launch3_v<16, 1>(a, M, st) : (L == 2 ? launch3_v<16, 2>(a, M, st) : launch3_v<16, 3>(a, M, st));
+    const int rc = dispatch_hl(D, L, [&](auto h, auto l) { return launch3_v<h(), l()>(a, M, st); });
     if (rc != TNF_OK) return rc;
     return check_launch("flow_fused3");
 }

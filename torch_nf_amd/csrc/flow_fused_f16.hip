@@ -21,7 +21,7 @@
 //                      which is exactly where the previous accumulator left them)
 #include "f16_tile.h"
 #include "support_math.h"
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -435,25 +435,13 @@ flow_fused_f16_kernel(FlowF16Args a) {
     }
 }
 
-template <int H, int L>
-static void launch_images16(const float* params, float* images, int64_t Mp, int S, int U, int64_t pstride,
-                            int64_t slot, hipStream_t st) {
-    hipLaunchKernelGGL((flow_images_f16_kernel<H, L>), grid_xm(2 * S, Mp), dim3(64), 0, st,
-                       params, images, S, U, pstride, slot, Mp);
-}
-
 int launch_flow_images_f16(const float* params, float* images, int64_t Mp, int D, int S, int L, int U,
                            int64_t pstride, hipStream_t st) {
     const int64_t slot = mfma_image_floats(D, 3);
-    if (D == 64) {
-        if (L == 1) launch_images16<32, 1>(params, images, Mp, S, U, pstride, slot, st);
-        else if (L == 2) launch_images16<32, 2>(params, images, Mp, S, U, pstride, slot, st);
-        else launch_images16<32, 3>(params, images, Mp, S, U, pstride, slot, st);
-    } else {
-        if (L == 1) launch_images16<16, 1>(params, images, Mp, S, U, pstride, slot, st);
-        else if (L == 2) launch_images16<16, 2>(params, images, Mp, S, U, pstride, slot, st);
-        else launch_images16<16, 3>(params, images, Mp, S, U, pstride, slot, st);
-    }
+    dispatch_hl(D, L, [&](auto h, auto l) {
+        hipLaunchKernelGGL((flow_images_f16_kernel<h(), l()>), grid_xm(2 * S, Mp), dim3(64), 0, st, params, images, S, U,
+                           pstride, slot, Mp);
+    });
     return check_launch("flow_images_f16");
 }
 
@@ -461,37 +449,8 @@ template <int H, int L, bool INV, int NT, int NW, int SS = 0>
 static int launch16_t(const FlowF16Args& a, int64_t M, hipStream_t st) {
     const size_t smem = (size_t)2 * a.S * (F16Image<H, L>::FLOATS + 2 * 2 * H) * sizeof(float) + 16 + NW * sizeof(float) +
                         7 * 2 * H * sizeof(float);
-    auto kern = flow_fused_f16_kernel<H, L, INV, NT, NW, SS>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return fail(TNF_ELAUNCH, "flow_fused_f16: cannot reserve %zu B of LDS", smem);
-    const int64_t ngroups = (a.N + 16 * NT - 1) / (16 * NT);
-    int64_t bx = (ngroups + NW - 1) / NW;
-    int64_t cap = (256 + M - 1) / M;
-    if (bx > cap) bx = cap;
-    hipLaunchKernelGGL(kern, grid_xm(bx, M), dim3(NW * 64), smem, st, a);
-    return TNF_OK;
-}
-
-template <int H, int L, bool INV>
-static int launch16_v(const FlowF16Args& a, int64_t M, int variant, hipStream_t st) {
-    if (L == 2) {
-        if (variant == 11) return launch16_t<H, L, INV, 1, 8>(a, M, st);
-        if (variant == 12) return launch16_t<H, L, INV, 1, 16>(a, M, st);
-        if (variant == 13) return launch16_t<H, L, INV, 2, 16>(a, M, st);
-        if (variant == 14) return launch16_t<H, L, INV, 2, 8>(a, M, st);  // run-time stage loop
-    }
-    // the reference's usual depth (num_stages = 4): layer loop fully unrolled, 3 % faster at D = 64
-    if (a.S == 4) return launch16_t<H, L, INV, 2, 8, 4>(a, M, st);
-    return launch16_t<H, L, INV, 2, 8>(a, M, st);
-}
-
-template <int H>
-static int launch16_h(const FlowF16Args& a, int L, int inverse, int64_t M, int variant, hipStream_t st) {
-    switch (L) {
-        case 1: return inverse ? launch16_v<H, 1, true>(a, M, variant, st) : launch16_v<H, 1, false>(a, M, variant, st);
-        case 2: return inverse ? launch16_v<H, 2, true>(a, M, variant, st) : launch16_v<H, 2, false>(a, M, variant, st);
-        default: return inverse ? launch16_v<H, 3, true>(a, M, variant, st) : launch16_v<H, 3, false>(a, M, variant, st);
-    }
+    const int64_t bx = persistent_bx_ceil((a.N + 16 * NT - 1) / (16 * NT), NW, 256, M);
+    return launch_lds("flow_fused_f16", flow_fused_f16_kernel<H, L, INV, NT, NW, SS>, grid_xm(bx, M), dim3(NW * 64), smem, st, a);
 }
 
 int launch_flow_fused_f16(const float* z, const float* images, const float* fold, const float* ldc,
@@ -507,7 +466,19 @@ int launch_flow_fused_f16(const float* z, const float* images, const float* fold
     FlowF16Args a{z, images, fold, ldc, z_out, sum_log_det, log_prob, Mz, Mp, N, mfma_image_floats(D, 3), S,
                   params, bn_mean, bn_alpha, pstride, fl.stage, fl.p_up + fl.p_low, fl.p_up, U, interval_consts};
     diag_count(TNF_DIAG_FLOW_F16);
-    int rc = (D == 64) ? launch16_h<32>(a, L, inverse, M, variant, st) : launch16_h<16>(a, L, inverse, M, variant, st);
+    const int rc = dispatch_hl(D, L, [&](auto h, auto l) {
+        return dispatch_bool(inverse, [&](auto inv) {
+            if (l() == 2) {
+                if (variant == 11) return launch16_t<h(), l(), inv(), 1, 8>(a, M, st);
+                if (variant == 12) return launch16_t<h(), l(), inv(), 1, 16>(a, M, st);
+                if (variant == 13) return launch16_t<h(), l(), inv(), 2, 16>(a, M, st);
+                if (variant == 14) return launch16_t<h(), l(), inv(), 2, 8>(a, M, st);  // run-time stage loop
+            }
+            // the reference's usual depth (num_stages = 4): layer loop fully unrolled, 3 % faster at D = 64
+            if (a.S == 4) return launch16_t<h(), l(), inv(), 2, 8, 4>(a, M, st);
+            return launch16_t<h(), l(), inv(), 2, 8>(a, M, st);
+        });
+    });
     if (rc != TNF_OK) return rc;
     return check_launch("flow_fused_f16");
 }

@@ -1,7 +1,7 @@
 // Shape- and dtype-generic kernels (any D, U, L; float32 / float64; M broadcast).
 // These are the coverage path: every shape the reference accepts runs here when
 // no MFMA specialisation exists (coupling_mfma.hip / flow_fused.hip hold those).
-#include "tnf_common.h"
+#include "launch.h"
 #include "wave_prims.h"
 
 namespace tnf {
@@ -113,21 +113,13 @@ int launch_coupling_generic(int dtype, const void* z, const void* params, void* 
     if (tiles > 0x7fffffff)
         return fail(TNF_EUNSUPPORTED, "coupling: grid too large (tiles=%lld, M=%lld)", (long long)tiles, (long long)M);
     const dim3 grid = grid_xm(tiles, M);
-    if (dtype == TNF_F32) {
-        if (smem > 64 * 1024)
-            (void)hipFuncSetAttribute((const void*)coupling_generic_kernel<float>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(coupling_generic_kernel<float>, grid, dim3(256), smem, st,
-                           (const float*)z, (const float*)params, (float*)z_out, (float*)log_det, Mz,
-                           Mp, N, D, L, U, upper, inverse, pstride, ld_mode, (int)TS, W);
-    } else {
-        if (smem > 64 * 1024)
-            (void)hipFuncSetAttribute((const void*)coupling_generic_kernel<double>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(coupling_generic_kernel<double>, grid, dim3(256), smem, st,
-                           (const double*)z, (const double*)params, (double*)z_out, (double*)log_det,
-                           Mz, Mp, N, D, L, U, upper, inverse, pstride, ld_mode, (int)TS, W);
-    }
+    const int rc = dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_lds("coupling_generic", coupling_generic_kernel<T>, grid, dim3(256), smem, st, (const T*)z,
+                          (const T*)params, (T*)z_out, (T*)log_det, Mz, Mp, N, D, L, U, upper, inverse, pstride, ld_mode,
+                          (int)TS, W);
+    });
+    if (rc != TNF_OK) return rc;
     return check_launch("coupling_generic");
 }
 
@@ -170,21 +162,14 @@ int launch_affine(int dtype, const void* z, const void* params, void* z_out, voi
     int64_t blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     if (blocks < 1) blocks = 1;
-    if (dtype == TNF_F32) {
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
         if (total > 0)
-            hipLaunchKernelGGL(affine_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st,
-                               (const float*)z, (const float*)params, (float*)z_out, Mz, Mp, N, D,
-                               inverse, pstride, total);
-        hipLaunchKernelGGL(affine_logdet_kernel<float>, dim3((unsigned)Mp), dim3(64), 0, st,
-                           (const float*)params, (float*)log_det, D, pstride);
-    } else {
-        if (total > 0)
-            hipLaunchKernelGGL(affine_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st,
-                               (const double*)z, (const double*)params, (double*)z_out, Mz, Mp, N, D,
-                               inverse, pstride, total);
-        hipLaunchKernelGGL(affine_logdet_kernel<double>, dim3((unsigned)Mp), dim3(64), 0, st,
-                           (const double*)params, (double*)log_det, D, pstride);
-    }
+            hipLaunchKernelGGL(affine_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)z, (const T*)params,
+                               (T*)z_out, Mz, Mp, N, D, inverse, pstride, total);
+        hipLaunchKernelGGL(affine_logdet_kernel<T>, dim3((unsigned)Mp), dim3(64), 0, st, (const T*)params, (T*)log_det, D,
+                           pstride);
+    });
     return check_launch("affine");
 }
 
@@ -219,14 +204,12 @@ int launch_bn_apply(int dtype, const void* z, const float* mean, const float* al
     const int64_t total = rows * D;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (total > 0) {
-        if (dtype == TNF_F32)
-            hipLaunchKernelGGL(bn_apply_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st,
-                               (const float*)z, mean, alpha, (float*)z_out, D, inverse, total);
-        else
-            hipLaunchKernelGGL(bn_apply_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st,
-                               (const double*)z, mean, alpha, (double*)z_out, D, inverse, total);
-    }
+    if (total > 0)
+        dispatch_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(bn_apply_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)z, mean, alpha,
+                               (T*)z_out, D, inverse, total);
+        });
     hipLaunchKernelGGL(bn_logdet_kernel, dim3(1), dim3(64), 0, st, alpha, log_det, D);
     return check_launch("bn_apply");
 }
@@ -383,8 +366,9 @@ static bool launch_bn_sums(const float* z, double* sums, int64_t rows, int D, in
         if (blocks > 512) blocks = 512;
         if (blocks < 1) blocks = 1;
         rpb = (rows + blocks - 1) / blocks;
-        hipLaunchKernelGGL(bn_stats_vec_kernel, dim3((unsigned)blocks), dim3(256), (size_t)rpi * 2 * D * sizeof(double), st, z,
-                           sums, rows, D, rpb, write_count);
+        // 16 KB of LDS at most (D <= 1024): below the opt-in, so launch_lds only launches and cannot fail
+        (void)launch_lds("bn_stats", bn_stats_vec_kernel, dim3((unsigned)blocks), dim3(256), (size_t)rpi * 2 * D * sizeof(double),
+                         st, z, sums, rows, D, rpb, write_count);
         return write_count != 0;
     }
     hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, z, sums, rows, D, rpb);
@@ -475,14 +459,12 @@ base_log_density_kernel(const T* __restrict__ omega, double* __restrict__ out, i
 int launch_base_log_density(int dtype, const void* omega, double* out, int64_t rows, int D, hipStream_t st) {
     int64_t blocks = (rows * 4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (rows > 0) {
-        if (dtype == TNF_F32)
-            hipLaunchKernelGGL(base_log_density_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st,
-                               (const float*)omega, out, rows, D);
-        else
-            hipLaunchKernelGGL(base_log_density_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st,
-                               (const double*)omega, out, rows, D);
-    }
+    if (rows > 0)
+        dispatch_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(base_log_density_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)omega, out,
+                               rows, D);
+        });
     return check_launch("base_log_density");
 }
 

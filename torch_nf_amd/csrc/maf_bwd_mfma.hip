@@ -16,7 +16,7 @@
 // parameter per workgroup.
 #include "mfma_tile.h"
 #include "support_math.h"
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -528,33 +528,6 @@ bool maf_bwd_mfma_supported(int D, int L, int U) {
     return maf_bwd_smem(maf_blayout(D, L, U)) <= 156 * 1024;
 }
 
-template <int DT, int UT>
-static int launch_maf_bwd_du(const MafBwdArgs& a, const MafBLayout& wl, dim3 grid, size_t smem, hipStream_t st) {
-    const bool vec = (a.D % 4) == 0;
-    if (vec) {
-        auto k = maf_bwd_mfma_kernel<DT, UT, true>;
-        if (smem > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail(TNF_ELAUNCH, "maf_bwd_mfma: cannot reserve %zu B of LDS", smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a, wl);
-    } else {
-        auto k = maf_bwd_mfma_kernel<DT, UT, false>;
-        if (smem > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail(TNF_ELAUNCH, "maf_bwd_mfma: cannot reserve %zu B of LDS", smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a, wl);
-    }
-    return TNF_OK;
-}
-
-template <int DT>
-static int launch_maf_bwd_d(const MafBwdArgs& a, const MafBLayout& wl, dim3 grid, size_t smem, hipStream_t st) {
-    switch (wl.UT) {
-        case 1: return launch_maf_bwd_du<DT, 1>(a, wl, grid, smem, st);
-        case 2: return launch_maf_bwd_du<DT, 2>(a, wl, grid, smem, st);
-        case 3: return launch_maf_bwd_du<DT, 3>(a, wl, grid, smem, st);
-        default: return launch_maf_bwd_du<DT, 4>(a, wl, grid, smem, st);
-    }
-}
-
 static int maf_bwd_nacc(int D, int L, int U) { return maf_bwd_smem(maf_blayout(D, L, U), 4) <= 156 * 1024 ? 4 : 1; }
 
 __global__ void __launch_bounds__(256)
@@ -583,7 +556,14 @@ static int launch_maf_bwd_args(MafBwdArgs& a, hipStream_t st) {
     if (a.Mp > 1) bx = 1;  // one workgroup owns the context's gradient row: plain stores
     else if (bx > 512) bx = 512;
     const dim3 grid = grid_xm(bx, a.M);
-    int rc = wl.DT == 1 ? launch_maf_bwd_d<1>(a, wl, grid, smem, st) : launch_maf_bwd_d<2>(a, wl, grid, smem, st);
+    auto go = [&](auto dt) {  // D <= 32: one or two feature tiles
+        return dispatch_1to4(wl.UT, [&](auto ut) {
+            return dispatch_bool((a.D % 4) == 0, [&](auto vec) {
+                return launch_lds("maf_bwd_mfma", maf_bwd_mfma_kernel<dt(), ut(), vec()>, grid, dim3(256), smem, st, a, wl);
+            });
+        });
+    };
+    const int rc = wl.DT == 1 ? go(int_c<1>{}) : go(int_c<2>{});
     if (rc != TNF_OK) return rc;
     return check_launch("maf_bwd_mfma");
 }

@@ -7,7 +7,7 @@
 // Packed parameters (bijectors.py:698-740): [W_mu0 | W_alpha0 | ... | W_mu_last | W_alpha_last],
 // W row-major [in][out]; `masks` holds one binary matrix per layer in the same order/shape
 // (D x U, (U x U) x (L-1), U x D), shared by both nets and by all parameter rows.
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -137,18 +137,12 @@ int launch_maf(int dtype, const void* z, const void* params, const void* masks, 
     const int64_t tiles = (N + TS - 1) / TS;
     if (tiles > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "maf: grid too large");
     const dim3 grid = grid_xm(tiles, M);
-    if (dtype == TNF_F32) {
-        auto k = maf_kernel<float>;
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, (const float*)z, (const float*)params, (const float*)masks,
-                           (float*)z_out, (float*)log_det, (float*)alpha_out, Mz, Mp, N, D, L, U, inverse, pstride, TS, W);
-    } else {
-        auto k = maf_kernel<double>;
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, (const double*)z, (const double*)params,
-                           (const double*)masks, (double*)z_out, (double*)log_det, (double*)alpha_out, Mz, Mp, N, D, L, U,
-                           inverse, pstride, TS, W);
-    }
+    const int rc = dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_lds("maf", maf_kernel<T>, grid, dim3(256), smem, st, (const T*)z, (const T*)params, (const T*)masks,
+                          (T*)z_out, (T*)log_det, (T*)alpha_out, Mz, Mp, N, D, L, U, inverse, pstride, TS, W);
+    });
+    if (rc != TNF_OK) return rc;
     return check_launch("maf");
 }
 
@@ -399,11 +393,7 @@ int launch_maf_backward(int dtype, const void* z, const void* params, const void
     if (lacc) {
         smem += (size_t)P * esz;
         if (Mp > 1) tiles = 1;  // one workgroup per context owns the row: plain stores, no atomics
-        else {
-            int64_t cap = 1024 / M;
-            if (cap < 1) cap = 1;
-            if (tiles > cap) tiles = cap;
-        }
+        else tiles = persistent_bx(tiles, 1, 1024, M);
     }
     void* partials = nullptr;
     int G = 1;
@@ -419,21 +409,14 @@ int launch_maf_backward(int dtype, const void* z, const void* params, const void
         tiles = G;
     }
     const dim3 grid = grid_xm(tiles, M);
-    if (dtype == TNF_F32) {
-        auto k = maf_backward_kernel<float>;
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, (const float*)z, (const float*)params, (const float*)masks,
-                           (const float*)g_zout, (const float*)g_ld, (float*)g_z, (float*)g_params, M, Mp, N, D, L,
-                           U, pstride, gpstride, TS, W, lacc, lw, (int)P, (float*)partials, det);
-    } else {
-        auto k = maf_backward_kernel<double>;
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, (const double*)z, (const double*)params,
-                           (const double*)masks, (const double*)g_zout, (const double*)g_ld, (double*)g_z,
-                           (double*)g_params, M, Mp, N, D, L, U, pstride, gpstride, TS, W, lacc, lw, (int)P,
-                           (double*)partials, det);
-    }
-    const int rc = check_launch("maf_backward");
+    int rc = dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_lds("maf_backward", maf_backward_kernel<T>, grid, dim3(256), smem, st, (const T*)z, (const T*)params,
+                          (const T*)masks, (const T*)g_zout, (const T*)g_ld, (T*)g_z, (T*)g_params, M, Mp, N, D, L, U, pstride,
+                          gpstride, TS, W, lacc, lw, (int)P, (T*)partials, det);
+    });
+    if (rc != TNF_OK) return rc;
+    rc = check_launch("maf_backward");
     if (rc || !partials) return rc;
     return launch_backward_reduce(dtype, partials, g_params, rows, G, P, gpstride, st);
 }

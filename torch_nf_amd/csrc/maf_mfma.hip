@@ -11,6 +11,7 @@
 // conditional flows), each wave walks 16-sample tiles.  Optional per-feature FMAs before (`pre`: the
 // folded Affine^-1 . BatchNorm^-1 of NormFlow('AR').log_prob) and after (`post`: BatchNorm . Affine of the
 // frozen forward), and the base-density epilogue, make NormFlow('AR') one kernel per call.
+#include "launch.h"
 #include "maf_tile.h"
 #include "support_math.h"
 
@@ -268,36 +269,6 @@ bool maf_mfma_supported(int D, int L, int U) {
     return (size_t)(11 * 16 * wl.DT + wl.floats()) * sizeof(float) <= 150 * 1024;
 }
 
-template <int DT, int UT>
-static int launch_maf_du(const MafArgs& a, const MafLayout& wl, dim3 grid, size_t smem, hipStream_t st) {
-    const bool vec = (a.D % 4) == 0;
-#define TNF_MAF_GO(INV, VEC)                                                                                     \
-    do {                                                                                                         \
-        auto k = maf_mfma_kernel<DT, UT, INV, VEC>;                                                              \
-        if (smem > 64 * 1024 &&                                                                                  \
-            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) \
-            return fail(TNF_ELAUNCH, "maf_mfma: cannot reserve %zu B of LDS", smem);                             \
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a, wl);                                                 \
-    } while (0)
-    if (a.inverse) {
-        if (vec) TNF_MAF_GO(true, true); else TNF_MAF_GO(true, false);
-    } else {
-        if (vec) TNF_MAF_GO(false, true); else TNF_MAF_GO(false, false);
-    }
-#undef TNF_MAF_GO
-    return TNF_OK;
-}
-
-template <int DT>
-static int launch_maf_d(const MafArgs& a, const MafLayout& wl, dim3 grid, size_t smem, hipStream_t st) {
-    switch (wl.UT) {
-        case 1: return launch_maf_du<DT, 1>(a, wl, grid, smem, st);
-        case 2: return launch_maf_du<DT, 2>(a, wl, grid, smem, st);
-        case 3: return launch_maf_du<DT, 3>(a, wl, grid, smem, st);
-        default: return launch_maf_du<DT, 4>(a, wl, grid, smem, st);
-    }
-}
-
 int launch_maf_mfma(const MafArgs& a, hipStream_t st) {
     if (!maf_mfma_supported(a.D, a.L, a.U))
         return fail(TNF_EUNSUPPORTED, "maf_mfma: no kernel for D=%d L=%d U=%d", a.D, a.L, a.U);
@@ -306,18 +277,16 @@ int launch_maf_mfma(const MafArgs& a, hipStream_t st) {
     const MafLayout wl = maf_layout(a.D, a.L, a.U);
     const size_t smem = (size_t)(11 * 16 * wl.DT + wl.floats()) * sizeof(float);
     const int64_t ntiles = (a.N + 15) / 16;
-    int64_t bx = (ntiles + 3) / 4;
-    int64_t cap = 2048 / M;
-    if (cap < 1) cap = 1;
-    if (bx > cap) bx = cap;
-    const dim3 grid = grid_xm(bx, M);
-    int rc;
-    switch (wl.DT) {
-        case 1: rc = launch_maf_d<1>(a, wl, grid, smem, st); break;
-        case 2: rc = launch_maf_d<2>(a, wl, grid, smem, st); break;
-        case 3: rc = launch_maf_d<3>(a, wl, grid, smem, st); break;
-        default: rc = launch_maf_d<4>(a, wl, grid, smem, st); break;
-    }
+    const dim3 grid = grid_xm(persistent_bx(ntiles, 4, 2048, M), M);
+    const int rc = dispatch_1to4(wl.DT, [&](auto dt) {
+        return dispatch_1to4(wl.UT, [&](auto ut) {
+            return dispatch_bool(a.inverse, [&](auto inv) {
+                return dispatch_bool((a.D % 4) == 0, [&](auto vec) {
+                    return launch_lds("maf_mfma", maf_mfma_kernel<dt(), ut(), inv(), vec()>, grid, dim3(256), smem, st, a, wl);
+                });
+            });
+        });
+    });
     if (rc != TNF_OK) return rc;
     return check_launch("maf_mfma");
 }

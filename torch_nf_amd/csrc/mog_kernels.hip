@@ -27,7 +27,7 @@
 // its N < 64 samples in order and owns its gradient row in LDS, which leaves coalesced -- no reduction.  Shared row:
 // every workgroup owns one partial row; each entry of it is owned by one thread, which adds the tile's samples in
 // sample order; an ordered pass adds the partial rows (the mechanism of ef_geta_partial_kernel).  No float atomics.
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -660,7 +660,7 @@ static int mog_lane_rows(int D, int K, int copies, int extra) {  // contexts per
 
 #define MOG_CASE(Dv, KERNEL, ...)                                                          \
     case Dv:                                                                               \
-        hipLaunchKernelGGL((KERNEL<Dv, SAMPLE>), grid, dim3(MOG_TILE), smem, st, __VA_ARGS__); \
+        if (launch_lds(what, KERNEL<Dv, SAMPLE>, grid, dim3(MOG_TILE), smem, st, __VA_ARGS__)) return TNF_ELAUNCH; \
         break;
 #define MOG_SWITCH(KERNEL, ...)                                                                                      \
     switch (D) {                                                                                                     \
@@ -771,7 +771,7 @@ int64_t mog_bwd_workspace(int64_t M, int64_t Mp, int64_t N, int D, int K) {
 
 #define MOG_BWD_CASE(Dv, KERNEL, ...)                                                    \
     case Dv:                                                                             \
-        hipLaunchKernelGGL((KERNEL<Dv>), grid, dim3(MOG_TILE), pl.smem, st, __VA_ARGS__); \
+        if (launch_lds("mog_log_prob_backward", KERNEL<Dv>, grid, dim3(MOG_TILE), pl.smem, st, __VA_ARGS__)) return TNF_ELAUNCH; \
         break;
 #define MOG_BWD_SWITCH(KERNEL, ...)                                                                                  \
     switch (pl.fused ? D : 0) {                                                                                      \

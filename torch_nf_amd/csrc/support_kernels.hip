@@ -5,7 +5,7 @@
 // Both are HBM-bound elementwise maps with a per-row log-det: a workgroup stages R rows through LDS so
 // that every global access is coalesced (thread <-> element) and the row reduction runs thread <-> row.
 // Algorithmic bytes per row: ToInterval 2*D*sizeof(T) + sizeof(T); ToSimplex (2*D_in + 2)*sizeof(T).
-#include "tnf_common.h"
+#include "launch.h"
 
 namespace tnf {
 
@@ -139,15 +139,14 @@ int launch_to_interval(int dtype, const void* z, const float* consts, void* z_ou
     if (smem > 64 * 1024) return fail(TNF_EUNSUPPORTED, "to_interval: D=%d needs %zu B of LDS per row", D, smem);
     const int64_t blocks = (rows + R - 1) / R;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "to_interval: grid too large");
-#define TNF_IV_LAUNCH(T, INV)                                                                                   \
-    hipLaunchKernelGGL((to_interval_kernel<T, INV>), dim3((unsigned)blocks), dim3(256), smem, st, (const T*)z, \
-                       consts, (T*)z_out, (T*)log_det, rows, D, R)
-    if (dtype == TNF_F32) {
-        if (inverse) TNF_IV_LAUNCH(float, true); else TNF_IV_LAUNCH(float, false);
-    } else {
-        if (inverse) TNF_IV_LAUNCH(double, true); else TNF_IV_LAUNCH(double, false);
-    }
-#undef TNF_IV_LAUNCH
+    const int rc = dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return dispatch_bool(inverse, [&](auto inv) {
+            return launch_lds("to_interval", to_interval_kernel<T, inv()>, dim3((unsigned)blocks), dim3(256), smem, st,
+                              (const T*)z, consts, (T*)z_out, (T*)log_det, rows, D, R);
+        });
+    });
+    if (rc != TNF_OK) return rc;
     return check_launch("to_interval");
 }
 
@@ -157,15 +156,13 @@ int launch_to_interval_backward(int dtype, const void* z, const float* consts, c
     if (total == 0) return 0;
     const int64_t blocks = (total + 255) / 256;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "to_interval_backward: grid too large");
-#define TNF_IV_LAUNCH(T, INV)                                                                                  \
-    hipLaunchKernelGGL((to_interval_backward_kernel<T, INV>), dim3((unsigned)blocks), dim3(256), 0, st,       \
-                       (const T*)z, consts, (const T*)g_zout, (const T*)g_ld, (T*)g_z, total, D)
-    if (dtype == TNF_F32) {
-        if (inverse) TNF_IV_LAUNCH(float, true); else TNF_IV_LAUNCH(float, false);
-    } else {
-        if (inverse) TNF_IV_LAUNCH(double, true); else TNF_IV_LAUNCH(double, false);
-    }
-#undef TNF_IV_LAUNCH
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        dispatch_bool(inverse, [&](auto inv) {
+            hipLaunchKernelGGL((to_interval_backward_kernel<T, inv()>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)z,
+                               consts, (const T*)g_zout, (const T*)g_ld, (T*)g_z, total, D);
+        });
+    });
     return check_launch("to_interval_backward");
 }
 
@@ -271,12 +268,12 @@ int launch_to_simplex(int dtype, const void* z, void* z_out, void* log_det, int6
     if (smem > 64 * 1024) return fail(TNF_EUNSUPPORTED, "to_simplex: D=%d needs %zu B of LDS per row", Din, smem);
     const int64_t blocks = (rows + R - 1) / R;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "to_simplex: grid too large");
-    if (dtype == TNF_F32)
-        hipLaunchKernelGGL(to_simplex_kernel<float>, dim3((unsigned)blocks), dim3(256), smem, st, (const float*)z,
-                           (float*)z_out, (float*)log_det, rows, Din, Dc, R);
-    else
-        hipLaunchKernelGGL(to_simplex_kernel<double>, dim3((unsigned)blocks), dim3(256), smem, st, (const double*)z,
-                           (double*)z_out, (double*)log_det, rows, Din, Dc, R);
+    const int rc = dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_lds("to_simplex", to_simplex_kernel<T>, dim3((unsigned)blocks), dim3(256), smem, st, (const T*)z,
+                          (T*)z_out, (T*)log_det, rows, Din, Dc, R);
+    });
+    if (rc != TNF_OK) return rc;
     return check_launch("to_simplex");
 }
 
@@ -290,13 +287,12 @@ int launch_to_simplex_backward(int dtype, const void* z, const void* g_zout, con
         return fail(TNF_EUNSUPPORTED, "to_simplex_backward: D=%d needs %zu B of LDS per row", Din, smem);
     const int64_t blocks = (rows + R - 1) / R;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "to_simplex_backward: grid too large");
-    if (dtype == TNF_F32)
-        hipLaunchKernelGGL(to_simplex_backward_kernel<float>, dim3((unsigned)blocks), dim3(256), smem, st,
-                           (const float*)z, (const float*)g_zout, (const float*)g_ld, (float*)g_z, rows, Din, Dc, R);
-    else
-        hipLaunchKernelGGL(to_simplex_backward_kernel<double>, dim3((unsigned)blocks), dim3(256), smem, st,
-                           (const double*)z, (const double*)g_zout, (const double*)g_ld, (double*)g_z, rows, Din, Dc,
-                           R);
+    const int rc = dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_lds("to_simplex_backward", to_simplex_backward_kernel<T>, dim3((unsigned)blocks), dim3(256), smem, st,
+                          (const T*)z, (const T*)g_zout, (const T*)g_ld, (T*)g_z, rows, Din, Dc, R);
+    });
+    if (rc != TNF_OK) return rc;
     return check_launch("to_simplex_backward");
 }
 
