@@ -30,6 +30,8 @@ DIAG_FAMILIES = 18
 EF_MVN, EF_DIRICHLET = 0, 1
 EF_COUNT_DOT, EF_COUNT_DOT_BWD = 0, 1  # tnf_ef_launch_count
 MOG_COUNT_LOGPROB, MOG_COUNT_LOGPROB_BWD, MOG_COUNT_SAMPLE = 0, 1, 2  # tnf_mog_launch_count
+ABC_COUNT_SMC, ABC_COUNT_PROPOSE, ABC_COUNT_NOISE = 0, 1, 2  # tnf_abc_launch_count
+ABC_MAX_D, ABC_MAX_SMC_D, ABC_MAX_TRIALS = 21, 6, 1 << 24  # include/tnf_abc.h
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
@@ -168,6 +170,15 @@ MOG_SIGNATURES = {
     "tnf_mog_sample_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _vp]),
 }
 
+# the rejection-ABC family, declared in include/tnf_abc.h: again a table of its own (tests/test_abc_host.py)
+ABC_SIGNATURES = {
+    "tnf_abc_supported": (ctypes.c_int, [_i32]),
+    "tnf_abc_launch_count": (_i64, [_i32]),
+    "tnf_abc_smc_mat_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp]),
+    "tnf_abc_propose_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp]),
+    "tnf_abc_noise_f32": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -177,10 +188,11 @@ def _load():
             "There is no non-HIP fallback." % LIB_PATH
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(MOG_SIGNATURES.items()):
-        fn = getattr(lib, name)  # AttributeError here = header / library out of step
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)  # AttributeError here = header / library out of step
+            fn.restype = res
+            fn.argtypes = args
     return lib
 
 

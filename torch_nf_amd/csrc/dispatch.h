@@ -45,6 +45,15 @@ template <class F> auto dispatch_dtype(int dtype, F&& f) {
     return dtype == TNF_F32 ? f(float{}) : f(double{});
 }
 
+// LO .. HI, one case each (the caller has checked the range; anything above goes to HI)
+template <int LO, int HI, class F> auto dispatch_range(int n, F&& f) {
+    if constexpr (LO == HI) {
+        return f(int_c<LO>{});
+    } else {
+        return n == LO ? f(int_c<LO>{}) : dispatch_range<LO + 1, HI>(n, f);
+    }
+}
+
 // grid.x of a persistent kernel: one workgroup per `per_wg` items, at most budget / M (and at least one) per context.
 // Pure arithmetic, kept here beside the dispatchers so that the CPU test reaches it without HIP.
 inline int64_t persistent_bx(int64_t items, int64_t per_wg, int64_t budget, int64_t M) {

@@ -21,6 +21,11 @@ averaged with ONE flattened all-reduce per step (distributed.allreduce_gradients
 The ranks start from the same context network (broadcast from rank 0) and apply the same averaged gradient, so their
 models stay bit-identical; no other collective is needed.  Steps run eagerly in this mode (a captured collective is
 not something this package relies on).
+
+`ABC_SMC` and `ABC_MCMC` are the rejection-ABC baselines the reference compares APT with (scripts/smcabc_mat.py calls
+`ABC_SMC(N, mat, proposal, T_x0, all_eps)`; notebooks/ABC-MCMC.ipynb defines both in cells 3 and 7).  Restated here on
+one fused HIP kernel (include/tnf_abc.h): in that ABC_SMC particle i of round t is always proposed from particle i of
+round t - 1 -- no resampling, no weights -- so the N chains are independent and all rounds run in one launch.
 """
 import time
 
@@ -216,3 +221,86 @@ def train_SNPE(cde, system, x0, M=1000, R=4, num_iters=1000, lr=1e-3, num_sims=N
         if verbose and rank == 0:
             print("round %d: %d pairs, loss %.4f" % (r, n, float(torch.stack(losses[-max(1, num_iters // 10):]).mean())))
     return torch.stack(losses).cpu().numpy() if losses else np.zeros(0)
+
+
+def _abc_inputs(system, proposal, T_x0, eps, max_trials):
+    """Checks shared by the two ABC drivers -> the float32 tensors of one kernel call (chol, bounds, x0, eps)."""
+    from .systems import GaussianProposal, Mat
+
+    if type(system) is not Mat:
+        raise ValueError("the ABC kernel simulates systems.Mat only (exactly that class), got %s" % type(system).__name__)
+    if system.noise != 0.0:
+        raise ValueError("the ABC kernel simulates Mat without observation noise: noise must be 0, got %g" % system.noise)
+    if not 2 <= system.d <= 6:
+        raise ValueError("the ABC kernel serves Mat(d) for 2 <= d <= 6 (D <= 21), got d=%d" % system.d)
+    if not isinstance(proposal, GaussianProposal) or proposal.D != system.D:
+        raise ValueError("proposal must be a systems.GaussianProposal over the system's D=%d parameters" % system.D)
+    if type(max_trials) is not int or not 1 <= max_trials <= 1 << 24:
+        raise ValueError("max_trials must be an int in 1 .. 2^24, got %r" % (max_trials,))
+    x0 = np.asarray(T_x0, dtype=np.float64).reshape(-1)
+    eps = np.asarray(eps, dtype=np.float64)
+    if x0.shape != (system.D_x,) or eps.ndim != 2 or eps.shape[1] != system.D_x:
+        raise ValueError("T_x0 must hold %d statistics and eps one row of %d tolerances per round, got shapes %s and %s"
+                         % (system.D_x, system.D_x, np.shape(T_x0), eps.shape))
+    f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32))
+    return f32(proposal.L), f32(np.stack((proposal.lb, proposal.ub))), f32(x0), f32(eps)
+
+
+def _abc_seed(seed):
+    return int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
+
+
+def ABC_SMC(N, system, proposal, T_x0, all_eps, seed=None, max_trials=1 << 16, return_info=False):
+    """The reference's ABC-SMC variant (notebooks/ABC-MCMC.ipynb cell 7; called by scripts/smcabc_mat.py): `z_last =
+    system.prior.rvs(N)` (host, np.random), then for each row eps_t of all_eps (T, D_x) and each particle i the first
+    candidate `proposal.rvs(z_last[i])` with `system.abc_accept(system.simulate(z), T_x0, eps_t)` becomes z_t[i].
+    One kernel launch for all T rounds of all N particles.
+
+    :return: zs (T + 1, N, D) float64 numpy, zs[0] the prior draw -- or None if any chain used up `max_trials`
+        candidates in a round (the notebook loops forever there; the script tests `zs is not None`).  With
+        return_info: (zs, T_xs (T + 1, N, D_x), trials (T, N) the number of candidates each acceptance took); a failed
+        run is then (None, None, trials), trials 0 from the round a chain gave up in.
+    seed None: one draw from np.random (after the prior draw), so np.random.seed governs the whole call.  There is no
+    CPU path: type(system) must be systems.Mat with noise == 0 and 2 <= d <= 6."""
+    from . import abc_ops
+
+    chol, bounds, x0, eps = _abc_inputs(system, proposal, T_x0, all_eps, max_trials)
+    if type(N) is not int or N < 1:
+        raise ValueError("N must be a positive int.")
+    z_last = np.asarray(system.prior.rvs(N), dtype=np.float64)
+    seed = _abc_seed(seed)
+    zs, xs, trials = abc_ops.abc_smc_mat(torch.as_tensor(z_last.astype(np.float32)), chol, bounds, x0, eps, system.d,
+                                         max_trials, seed)
+    trials = trials.cpu().numpy()
+    if (trials == 0).any():
+        return (None, None, trials) if return_info else None
+    zs = np.concatenate((z_last[None], zs.cpu().numpy().astype(np.float64)))
+    if not return_info:
+        return zs
+    T_xs = np.concatenate((system.simulate(z_last)[None], xs.cpu().numpy().astype(np.float64)))
+    return zs, T_xs, trials
+
+
+def ABC_MCMC(N, system, proposal, T_x0, eps, chains=1, seed=None, max_trials=1 << 16):
+    """ABC-MCMC (notebooks/ABC-MCMC.ipynb cell 3): N states of a chain started at a prior draw.  The notebook accepts
+    an ABC-accepted candidate z with the Metropolis ratio p(z) q(z_last | z) / (p(z_last) q(z | z_last)); with the
+    uniform prior (both points lie inside the box) and the symmetric, UNtruncated `proposal.logpdf`, that log-ratio is
+    identically 0, so every ABC-accepted candidate is taken: a chain is "the first ABC-accepted candidate from z_last",
+    N times at one eps -- the ABC_SMC kernel with `chains` particles and T = N rounds, one launch.
+
+    :return: (zs (N, D), T_xs (N, 2)) for chains == 1, (chains, N, D) and (chains, N, 2) otherwise; None if a chain used
+        up `max_trials` candidates for one state."""
+    from . import abc_ops
+
+    eps = np.asarray(eps, dtype=np.float64).reshape(1, -1)
+    if type(N) is not int or N < 1 or type(chains) is not int or chains < 1:
+        raise ValueError("N and chains must be positive ints.")
+    chol, bounds, x0, eps_t = _abc_inputs(system, proposal, T_x0, np.repeat(eps, N, axis=0), max_trials)
+    z_last = np.asarray(system.prior.rvs(chains), dtype=np.float64)
+    zs, xs, trials = abc_ops.abc_smc_mat(torch.as_tensor(z_last.astype(np.float32)), chol, bounds, x0, eps_t, system.d,
+                                         max_trials, _abc_seed(seed))
+    if bool((trials == 0).any()):
+        return None
+    zs = zs.cpu().numpy().astype(np.float64).transpose(1, 0, 2)
+    xs = xs.cpu().numpy().astype(np.float64).transpose(1, 0, 2)
+    return (zs[0], xs[0]) if chains == 1 else (zs, xs)
