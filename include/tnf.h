@@ -632,4 +632,5 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
 /* the mixture-of-Gaussians entries (density_estimator.py:57-237): a family and a header of its own */
 #include "tnf_mog.h"
 #include "tnf_abc.h"
+#include "tnf_hebb.h"
 #endif /* TNF_H */

@@ -15,13 +15,13 @@ from .bijectors import MAF, ToInterval, ToSimplex, Affine, BatchNorm, Bijector, 
 from .conditional_density_estimator import ConditionalDensityEstimator
 from .density_estimator import DensityEstimator, MoG, NormFlow
 from .exponential_families import MVN, Dirichlet, ExponentialFamily
-from .lfi import ABC_MCMC, ABC_SMC
-from .systems import GaussianProposal, Mat
+from .lfi import ABC_MCMC, ABC_SMC, train_nde
+from .systems import GaussianProposal, HebbLearn, Mat
 
 __version__ = "0.1.0"
 __all__ = ["Bijector", "RealNVP", "MAF", "ToInterval", "ToSimplex", "Affine", "BatchNorm", "DensityEstimator", "NormFlow", "MoG",
            "ConditionalDensityEstimator", "ExponentialFamily", "MVN", "Dirichlet", "exponential_families",
-           "ABC_SMC", "ABC_MCMC", "GaussianProposal", "Mat", "install_as_torch_nf"]
+           "ABC_SMC", "ABC_MCMC", "GaussianProposal", "Mat", "HebbLearn", "train_nde", "install_as_torch_nf"]
 
 
 def install_as_torch_nf():

@@ -32,6 +32,8 @@ EF_COUNT_DOT, EF_COUNT_DOT_BWD = 0, 1  # tnf_ef_launch_count
 MOG_COUNT_LOGPROB, MOG_COUNT_LOGPROB_BWD, MOG_COUNT_SAMPLE = 0, 1, 2  # tnf_mog_launch_count
 ABC_COUNT_SMC, ABC_COUNT_PROPOSE, ABC_COUNT_NOISE = 0, 1, 2  # tnf_abc_launch_count
 ABC_MAX_D, ABC_MAX_SMC_D, ABC_MAX_TRIALS = 21, 6, 1 << 24  # include/tnf_abc.h
+HEBB_COUNT_SIM, HEBB_COUNT_NOISE = 0, 1  # tnf_hebb_launch_count
+HEBB_MAX_N = 64  # include/tnf_hebb.h
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
@@ -179,6 +181,15 @@ ABC_SIGNATURES = {
     "tnf_abc_noise_f32": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
 }
 
+# the Hebbian learning-rule simulator, declared in include/tnf_hebb.h: a fourth table (tests/test_hebb_host.py)
+HEBB_SIGNATURES = {
+    "tnf_hebb_supported": (ctypes.c_int, [_i32]),
+    "tnf_hebb_launch_count": (_i64, [_i32]),
+    "tnf_hebb_simulate_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
+                                             _i64, _i64, _f32, _vp]),
+    "tnf_hebb_noise_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -188,7 +199,7 @@ def _load():
             "There is no non-HIP fallback." % LIB_PATH
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES):
+    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

@@ -223,6 +223,90 @@ def train_SNPE(cde, system, x0, M=1000, R=4, num_iters=1000, lr=1e-3, num_sims=N
     return torch.stack(losses).cpu().numpy() if losses else np.zeros(0)
 
 
+def train_nde(cde, system, x0, N=500, R=4, num_iters=1000, lr=1e-4, clip=None, use_graph=None, verbose=False):
+    """`train_nde` of the reference's notebooks/LFI_learning_rules.ipynb (cell 16), restated literally with the
+    simulator inside the optimisation step and the whole step on the device.  Every iteration of every round draws N
+    fresh parameter sets -- in round 1 from the prior (`system.sample_prior_device`), in later rounds from the current
+    posterior estimate `cde.sample(x0, N)` under no_grad -- simulates them (`system.simulate_device(z, t_dev=counter)`,
+    draw `counter` of the system's noise stream, incremented on the device inside the step) and minimises
+
+        loss = - mean_i log q(z_i | x_i) = -mean(cde.log_prob(z[:, None, :], x)),
+
+    then backward, the optional clamp of every gradient entry to [-clip, clip] (cell 15; the notebook passes 1e10) and
+    Adam.  Non-finite simulations are not filtered, as in the notebook.
+
+    :param system: object with D_x, sample_prior_device(N) -> (z, log_p) and simulate_device(z, t_dev=) on the HIP
+        device (systems.HebbLearn).  :param x0: (1, D_x) observation.
+    :param use_graph: replay each round's step as one HIP graph (graphs.GraphedStep, Adam with capturable=True);
+        default: on a HIP device.  A round whose step cannot be captured finishes its remaining steps eagerly
+        (the three warm-up steps before the capture count among the round's num_iters).
+    :return: losses, numpy (R * num_iters)."""
+    for name, v in (("N", N), ("R", R), ("num_iters", num_iters)):
+        if type(v) is not int or v < 1:
+            raise ValueError("train_nde: %s must be a positive int, got %r" % (name, v))
+    if clip is not None and not float(clip) > 0.0:
+        raise ValueError("train_nde: clip must be None or positive, got %r" % (clip,))
+    if not (hasattr(system, "simulate_device") and hasattr(system, "sample_prior_device")):
+        raise ValueError("train_nde: the system must simulate on the device (simulate_device, sample_prior_device), "
+                         "got %s" % type(system).__name__)
+    x0 = np.asarray(x0, dtype=np.float64)
+    if x0.ndim != 2 or x0.shape != (1, system.D_x):
+        raise ValueError("train_nde: x0 must be (1, D_x=%d), got shape %s" % (system.D_x, x0.shape))
+    dev = next(cde.param_net.parameters()).device
+    if use_graph is None:
+        use_graph = dev.type == "cuda"
+    x0_t = torch.as_tensor(x0, dtype=torch.float32, device=dev)
+    # capturable on a HIP device in both modes: the eager and the graphed run then take the same Adam arithmetic
+    opt = torch.optim.Adam(cde.param_net.parameters(), lr=lr, capturable=dev.type == "cuda")
+    net_params = [p for p in cde.param_net.parameters()]
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)  # the draw index of the simulator's stream
+    losses = []
+    for r in range(R):
+        def step():
+            if r == 0:
+                z, _ = system.sample_prior_device(N)
+            else:
+                with torch.no_grad():
+                    z_s, _ = cde.sample(x0_t, N=N)
+                z = z_s[0].detach()
+            x = system.simulate_device(z, t_dev=counter)
+            counter.add_(1)
+            loss = -torch.mean(cde.log_prob(z[:, None, :], x))
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            if clip is not None:
+                for p in net_params:
+                    p.grad.clamp_(-clip, clip)
+            opt.step()
+            return loss.detach()
+
+        done = 0
+        if use_graph and num_iters > 4:
+            from .graphs import GraphedStep
+
+            side = torch.cuda.Stream()  # three real steps on a side stream before the capture; their losses are kept
+            side.wait_stream(torch.cuda.current_stream())  # here, so a refused capture loses no step
+            with torch.cuda.stream(side):
+                for _ in range(3):
+                    losses.append(step().clone())
+            torch.cuda.current_stream().wait_stream(side)
+            done = 3
+            try:
+                gs = GraphedStep(step, warmup=0)
+                for _ in range(num_iters - done):
+                    losses.append(gs().clone())
+                    done += 1
+            except RuntimeError as e:  # a step this device / build cannot capture: finish the round eagerly
+                if verbose:
+                    print("round %d: graph capture unavailable (%s), running eagerly" % (r, str(e).splitlines()[0]))
+                torch.cuda.synchronize()
+        for _ in range(num_iters - done):
+            losses.append(step())
+        if verbose:
+            print("round %d: loss %.4f" % (r, float(torch.stack(losses[-max(1, num_iters // 10):]).mean())))
+    return torch.stack(losses).cpu().numpy()
+
+
 def _abc_inputs(system, proposal, T_x0, eps, max_trials):
     """Checks shared by the two ABC drivers -> the float32 tensors of one kernel call (chol, bounds, x0, eps)."""
     from .systems import GaussianProposal, Mat

@@ -10,6 +10,9 @@ The rejection-ABC baselines (scripts/smcabc_mat.py, notebooks/ABC-MCMC.ipynb) ad
 `GaussianProposal(Sigma, lb, ub)` -- defined in the notebook's cell 2, restated here with its draws on the HIP kernel
 of include/tnf_abc.h -- and `system.prior.rvs(N)` / `.logpdf(z)` and `system.abc_accept(T_x, T_x0, eps)`, of which
 again only the calls survive (cells 3, 7): PARITY UNPINNED like the rest.
+
+`HebbLearn` is the exception: the simulator of notebooks/LFI_learning_rules.ipynb survives in the snapshot (cell 8), and
+tests/golden/hebb.npz pins this package's arithmetic to it.
 """
 import numpy as np
 import torch
@@ -84,6 +87,135 @@ class _BoxPrior(object):
 
     def logpdf(self, z):
         return self._system.log_prior(z)
+
+
+class HebbLearn(object):
+    """The Hebbian learning-rule problem of the reference's notebooks/LFI_learning_rules.ipynb: parameters
+    z = (alpha, beta, theta_x, b), data x = the weights of `num_neurons` neurons after `num_passes` passes over `N_x`
+    shared inputs under `hebb` (cell 8), simulated by the HIP kernel of include/tnf_hebb.h.  Unlike the rest of this
+    module this one is pinned to the reference: tests/golden/hebb.npz holds the notebook function's own outputs.
+
+    `.D = 4`, `.D_x = num_neurons`, `.lb` / `.ub` / `.support_layer = ToInterval(4, lb, ub)` as in cell 4.  `.x`
+    (N_x, n) is drawn as cell 4 draws it -- Sigma ~ inverse-Wishart(df = 5 n, scale = df I), x ~ N(0, Sigma) -- through
+    exponential_families._inv_wishart (no scipy at run time): the same distribution, NOT the same stream as
+    scipy.stats under one np.random.seed.  `.w0 ~ N(0, 1)`.  `seed` keys the simulator's noise stream (None: one
+    draw from np.random, so np.random.seed governs the whole system).
+
+    The prior is `SNPE_prior` round 1 (cell 13): alpha, beta log-uniform on [1e-5, 1e-1], theta_x uniform on (-3, 3),
+    b uniform on (1, 20).  `log_prior` is the density of that draw, 1 / (z ln10 4) per log-uniform coordinate; the
+    notebook's `p_z = ln(10) z` is not a density (and its loss never uses it): a deliberate deviation."""
+
+    PRIOR_LOG10 = (-5.0, -1.0)   # alpha, beta: 10 ** uniform
+    PRIOR_THETA = (-3.0, 3.0)
+    PRIOR_B = (1.0, 20.0)
+
+    def __init__(self, num_neurons=20, N_x=50, num_passes=2, sigma_eps=1e-4, seed=None):
+        from .bijectors import ToInterval
+        from .exponential_families import _inv_wishart
+
+        if type(num_neurons) is not int or not 1 <= num_neurons <= 64:
+            raise ValueError("num_neurons must be an int in 1 .. 64 (include/tnf_hebb.h), got %r" % (num_neurons,))
+        if type(N_x) is not int or N_x < 1 or type(num_passes) is not int or num_passes < 1:
+            raise ValueError("N_x and num_passes must be positive ints.")
+        if not float(sigma_eps) >= 0.0:
+            raise ValueError("sigma_eps must be >= 0, got %r" % (sigma_eps,))
+        self.D = 4
+        self.D_x = num_neurons
+        self.num_neurons = num_neurons
+        self.N_x = N_x
+        self.num_passes = num_passes
+        self.n_steps = num_passes * N_x
+        self.sigma_eps = float(sigma_eps)
+        self.lb = np.array([1e-6, 1e-6, -4.0, 0.0])
+        self.ub = np.array([2e-1, 2e-1, 4.0, 20.0])
+        self.support_layer = ToInterval(self.D, self.lb, self.ub)
+        Sigma = _inv_wishart(1, num_neurons, 5 * num_neurons)[0]
+        self.x = np.random.multivariate_normal(np.zeros(num_neurons), Sigma, N_x)
+        self.w0 = np.random.normal(0.0, 1.0, (num_neurons,))
+        self.seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
+        self.prior = _BoxPrior(self)
+        self._t = 0          # draw index of the next simulate() call
+        self._dev = None     # (device, x, w0) float32 copies for the kernel
+        self._bounds_key, self._bounds = None, None        # log_prior: the prior box on the device of its argument
+        self._prior_key, self._prior_dev = None, None      # sample_prior_device: the box's corner and widths
+        self._prior_lo = np.array([self.PRIOR_LOG10[0], self.PRIOR_LOG10[0], self.PRIOR_THETA[0], self.PRIOR_B[0]])
+        self._prior_hi = np.array([self.PRIOR_LOG10[1], self.PRIOR_LOG10[1], self.PRIOR_THETA[1], self.PRIOR_B[1]])
+
+    # ---- the prior ----------------------------------------------------------------------------------------------------
+    def sample_prior(self, N):
+        """(N, 4) float64 from np.random, in the notebook's order of draws (alpha, beta, theta_x, b)."""
+        cols = [np.random.uniform(lo, hi, (N,)) for lo, hi in zip(self._prior_lo, self._prior_hi)]
+        cols[0], cols[1] = 10.0 ** cols[0], 10.0 ** cols[1]
+        return np.stack(cols, axis=1)
+
+    def _log_prior_const(self):
+        """log of: 1 / (ln10 * 4) twice, 1 / 6, 1 / 19 -- the density is this constant over alpha * beta."""
+        width = self._prior_hi - self._prior_lo
+        return float(-2.0 * np.log(np.log(10.0)) - np.sum(np.log(width)))
+
+    def log_prior(self, z):
+        """log density of the prior draw, -inf outside its box; z (..., 4) numpy or torch."""
+        c = self._log_prior_const()
+        lo = np.array([10.0 ** self._prior_lo[0], 10.0 ** self._prior_lo[1], self._prior_lo[2], self._prior_lo[3]])
+        hi = np.array([10.0 ** self._prior_hi[0], 10.0 ** self._prior_hi[1], self._prior_hi[2], self._prior_hi[3]])
+        if torch.is_tensor(z):
+            key = (z.dtype, z.device)  # device copies of the box are made once (and keep a step capturable)
+            if self._bounds_key != key:
+                self._bounds = (torch.as_tensor(lo, dtype=z.dtype, device=z.device),
+                                torch.as_tensor(hi, dtype=z.dtype, device=z.device))
+                self._bounds_key = key
+            tlo, thi = self._bounds
+            inside = ((z >= tlo) & (z <= thi)).all(-1)
+            lp = c - torch.log(z[..., 0]) - torch.log(z[..., 1])
+            return torch.where(inside, lp, torch.full_like(lp, -float("inf")))
+        z = np.asarray(z, dtype=np.float64)
+        inside = np.all((z >= lo) & (z <= hi), axis=-1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            lp = c - np.log(z[..., 0]) - np.log(z[..., 1])
+        return np.where(inside, lp, -np.inf)
+
+    def sample_prior_device(self, N, generator=None):
+        """(z (N, 4), log_prior (N)) float32 on the HIP device from the device RNG: no host work, capturable."""
+        from . import _lib
+
+        dev = _lib.require_device()
+        key = ("prior", dev)
+        if self._prior_key != key:
+            self._prior_dev = (torch.as_tensor(self._prior_lo, dtype=torch.float32, device=dev),
+                               torch.as_tensor(self._prior_hi - self._prior_lo, dtype=torch.float32, device=dev))
+            self._prior_key = key
+        lo, width = self._prior_dev
+        u = torch.rand((N, 4), dtype=torch.float32, device=dev, generator=generator) * width + lo
+        z = torch.cat((torch.pow(10.0, u[:, :2]), u[:, 2:]), dim=1)
+        log_p = self._log_prior_const() - 2.302585092994046 * (u[:, 0] + u[:, 1])
+        return z, log_p
+
+    # ---- the simulator --------------------------------------------------------------------------------------------------
+    def _device_inputs(self):
+        from . import _lib
+
+        dev = _lib.require_device()
+        if self._dev is None or self._dev[0] != dev:
+            self._dev = (dev, torch.as_tensor(self.x, dtype=torch.float32).to(dev).contiguous(),
+                         torch.as_tensor(self.w0, dtype=torch.float32).to(dev).reshape(1, -1).contiguous())
+        return self._dev
+
+    def simulate_device(self, z, t=0, t_dev=None, traj=False):
+        """z (N, 4) float32 tensor -> x (N, num_neurons) on the HIP device (with traj: (x, (n_steps, N, n))).  Draw t of
+        the system's noise stream, or the draw the device word t_dev holds.  No synchronisation: capturable."""
+        from . import hebb_ops
+
+        _, x, w0 = self._device_inputs()
+        return hebb_ops.hebb_simulate(z, x, w0, self.n_steps, self.sigma_eps, seed=self.seed, t=t, t_dev=t_dev, traj=traj)
+
+    def simulate(self, z, t=None):
+        """z (N, 4) numpy -> x (N, num_neurons) float64 numpy, computed on the GPU (there is no CPU path): the host
+        protocol of train_APT / train_SNPE.  t None: the next draw of the system's stream (a counter the call advances),
+        so that repeated calls see fresh noise."""
+        if t is None:
+            t, self._t = self._t, (self._t + 1) % (1 << 31)
+        z = torch.as_tensor(np.ascontiguousarray(np.asarray(z, dtype=np.float32).reshape(-1, 4)))
+        return self.simulate_device(z, t=t).cpu().numpy().astype(np.float64)
 
 
 class GaussianProposal(object):
