@@ -263,8 +263,21 @@ bn_stats_kernel(const float* __restrict__ z, double* __restrict__ sums, int64_t 
     }
 }
 
-// D % 4 == 0 and D <= 1024: 16-byte loads, D/4 lanes per row, float partial sums over short runs of rows
-// (64 values) folded into double accumulators -- same sums as bn_stats_kernel to ~1e-7 relative.
+// rows row, row + rpi, ..., row + 7 rpi of lane q's four features; zeros past r1
+__device__ __forceinline__ void bn_load8(float4 (&v)[8], const float* __restrict__ z, int64_t row, int64_t r1, int rpi, int D,
+                                         int q) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int64_t rw = row + u * (int64_t)rpi;
+        v[u] = rw < r1 ? *reinterpret_cast<const float4*>(z + rw * D + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// D % 4 == 0 and D <= 1024: 16-byte loads, D/4 lanes per row, eight rows in flight per lane.  Products and sums in
+// double, like bn_stats_kernel: every term x and x * x of a float x is exact in double, so the two routes differ by
+// the order of their double additions only (rows * 2^-53 relative to the sum of |terms|).  Float partial sums, which
+// this kernel once kept over runs of 64 values, put 1e-7 relative into sum x^2 and hence 1e-7 (mean / sd)^2 into
+// var_b = sum x^2 / n - mu^2: 2e-5 of alpha at mean 3, sd 0.05.
 __global__ void __launch_bounds__(256)
 bn_stats_vec_kernel(const float* __restrict__ z, double* __restrict__ sums, int64_t rows, int D,
                     int64_t rows_per_block, int write_count) {
@@ -278,27 +291,22 @@ bn_stats_vec_kernel(const float* __restrict__ z, double* __restrict__ sums, int6
     if (r1 > rows) r1 = rows;
     double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
     if (r < rpi) {
-        int64_t row = r0 + r;
-        while (row < r1) {
-            float a1[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int k = 0; k < 8 && row < r1; ++k, row += 8 * (int64_t)rpi) {
-                float4 v[8];  // eight rows in flight per lane
+        // eight rows in flight per lane, and the next eight requested before these are summed: with two workgroups per CU
+        // nothing else hides the 96 double operations of a round behind the loads
+        const int64_t step = 8 * (int64_t)rpi;
+        float4 v[8], nx[8];
+        bn_load8(v, z, r0 + r, r1, rpi, D, q);
+        for (int64_t row = r0 + r; row < r1; row += step) {
+            bn_load8(nx, z, row + step, r1, rpi, D, q);
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int64_t rw = row + u * (int64_t)rpi;
-                    v[u] = rw < r1 ? *reinterpret_cast<const float4*>(z + rw * D + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int u = 0; u < 8; ++u) {
+                const double x[4] = {(double)v[u].x, (double)v[u].y, (double)v[u].z, (double)v[u].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    s1[j] += x[j];
+                    s2[j] = fma(x[j], x[j], s2[j]);
                 }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    a1[0] += v[u].x; a1[1] += v[u].y; a1[2] += v[u].z; a1[3] += v[u].w;
-                    a2[0] = fmaf(v[u].x, v[u].x, a2[0]); a2[1] = fmaf(v[u].y, v[u].y, a2[1]);
-                    a2[2] = fmaf(v[u].z, v[u].z, a2[2]); a2[3] = fmaf(v[u].w, v[u].w, a2[3]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                s1[j] += (double)a1[j];
-                s2[j] += (double)a2[j];
+                v[u] = nx[u];
             }
         }
 #pragma unroll
