@@ -45,8 +45,26 @@
 #if TNF2_ABL == 4  // timing experiment only: split without remainder (scope: wave_prims.h)
 #define TNF_SPLIT_RNE_NO_REMAINDER 1
 #endif
+#include <type_traits>
+
 #include "f16_tile.h"
 #include "support_math.h"
+
+// Two pieces of per-layer bookkeeping taken off the vector pipe, each one rebuild away from the
+// form it replaces:
+//   TNF2_PSPLIT  a layer splits its output where it is produced, into the register of the dead fma result, and hands
+//                the packed halves to the next layer -- the in-place split of a conditioner half that stays live cost
+//                a v_mov per value.  Same instructions on the same values: bit-identical.  Ships: 0.2284 -> 0.2230 ms.
+//   TNF2_LDMFMA  the log-det sum(s) comes from one more K = 16 contraction per layer (weight row 0 = the column sums of
+//                the s-net's output weights) accumulated through all layers, instead of one v_add per feature.  Measured
+//                and NOT shipped: three more dependent MFMAs per tile and layer cost more than the eight adds they replace
+//                (alone 0.2338 ms, with TNF2_PSPLIT 0.2279).
+#ifndef TNF2_PSPLIT
+#define TNF2_PSPLIT 1
+#endif
+#ifndef TNF2_LDMFMA
+#define TNF2_LDMFMA 0
+#endif
 
 // Explicit pipe interleave of the layer body, all measured and none adopted -- DESIGN.md 3.11.2:
 //   1 / 2: __builtin_amdgcn_iglp_opt(0 / 1);  3: one MFMA then five vector instructions, 24 NT times per layer, as
@@ -93,26 +111,29 @@ __device__ __forceinline__ f4 sig2s_4(f4 v, float S) {
     return f4{sig2s(v[0], S), sig2s(v[1], S), sig2s(v[2], S), sig2s(v[3], S)};
 }
 
-// LDS image of one coupling layer (4-byte units)
-template <int H, int L>
+// LDS image of one coupling layer (4-byte units).  LDR: one more K = 16 group, the log-det row (row 0 = sum over the
+// features of the s-net's output weights, rows 1 .. 15 zero), and the sum of the s biases in the spare scale slot.
+template <int H, int L, bool LDR = false>
 struct Img2 {
     static constexpr int HT = H / 16;
     static constexpr int N0 = (H == 32) ? 4 : 0;                            // layer-0 groups of the K = 32 form
-    static constexpr int NK = ((H == 16) ? 2 : 0) + 2 * (L - 1) + 2 * HT;   // K = 16 contractions
+    static constexpr int NK = ((H == 16) ? 2 : 0) + 2 * (L - 1) + 2 * HT + (LDR ? 1 : 0);  // K = 16 contractions
     static constexpr int NBG = 2 + 2 * (L - 1) + 2 * HT;
     static constexpr int OFF_D = N0 * 256;          // [g][lane] 16 B: [w_hi(4) | w_lo(4)]
     static constexpr int OFF_B = OFF_D + NK * 256;  // [g][q][4] fp32 biases (accumulator initial values)
-    static constexpr int OFF_S = OFF_B + NBG * 16;  // 8 floats: sigmoid scales S[stage][net]
+    static constexpr int OFF_S = OFF_B + NBG * 16;  // 8 floats: sigmoid scales S[stage][net] (L <= 3: six); LDR: [6] = sum of the s biases
     static constexpr int OFF_A = OFF_S + 8;         // H floats: Ay * sigma of the transformed half; H more: By * sigma (forward)
     static constexpr int FLOATS = OFF_A + 2 * H;
     __device__ static constexpr int k_l0(int net) { return net; }  // H == 16 only
     __device__ static constexpr int k_h(int l, int net) { return ((H == 16) ? 2 : 0) + 2 * l + net; }
     __device__ static constexpr int k_o(int net, int mo) { return ((H == 16) ? 2 : 0) + 2 * (L - 1) + net * HT + mo; }
+    __device__ static constexpr int k_ld() { return NK - 1; }  // LDR only
     __device__ static constexpr int b_b0(int net) { return net; }
     __device__ static constexpr int b_bh(int l, int net) { return 2 + 2 * l + net; }
     __device__ static constexpr int b_b2(int net, int mo) { return 2 + 2 * (L - 1) + net * HT + mo; }
 };
 static_assert(Img2<32, 3>::FLOATS % 4 == 0 && Img2<16, 1>::FLOATS % 4 == 0, "images must stay 16-byte aligned");
+static_assert(Img2<32, 2, true>::FLOATS == Img2<32, 2>::FLOATS + 256, "the log-det row is one K = 16 group");
 
 // kappa of a layer: its layer-0 weights, with the activation folding (2 log2 e) and the fold A in front of the
 // conditioner half, scaled by 2^kappa have their largest magnitude in [1, 2).  One wave.
@@ -160,13 +181,15 @@ __device__ __forceinline__ void store_k16(u4* gd, const float (&v)[4]) {
 //   sig_next 2^-kappa_{k+1}: factor the transformed half is emitted with (1 for the last layer walked)
 //   din/dout real conditioner / transformed widths (< H only in the padded layouts: zero weight rows and columns, so
 //            padded s and t outputs are exactly 0; foldc / foldprev must be the identity on the padded features)
-template <int H, int L, int PREC = 0, bool FWD = false>
+//   LDR      also write the log-det row and the s-bias sum (Img2<H, L, true>)
+template <int H, int L, int PREC = 0, bool FWD = false, bool LDR = false>
 __device__ __forceinline__ void build_image2(float* img, const float* __restrict__ p, int U, int lane, const float* foldc,
                                              const float* foldprev, int c, float sc_in, float sc_prev, float sig_next,
                                              int din = H, int dout = H) {
-    typedef Img2<H, L> I;
+    typedef Img2<H, L, LDR> I;
     constexpr int D = 2 * H;
     constexpr int HT = I::HT;
+    static_assert(!LDR || L <= 3, "the s-bias sum takes the scale slot of a fourth stage");
     LayerW<H, L> w;
     load_layer_w<H, L>(w, p, U, lane, din, dout);
     const int q = lane >> 4;
@@ -238,6 +261,28 @@ __device__ __forceinline__ void build_image2(float* img, const float* __restrict
     // ---- write the image ----
     u4* g0 = reinterpret_cast<u4*>(img) + lane;
     u4* gd = reinterpret_cast<u4*>(img + I::OFF_D) + lane;
+    if constexpr (LDR) {
+        // the log-det row, from the s-net's output weights as they stand (S applied; padded columns are zero): this lane
+        // holds hidden units 4q + j of output rows 16 mo + r, the sum over mo and the 16 r-lanes goes to row 0 (r = 0)
+        float rs[4], sb = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float c = 0.f;
+#pragma unroll
+            for (int mo = 0; mo < HT; ++mo) {
+                c += w.w2[1][mo][j];
+                sb += w.b2[1][mo][j];
+            }
+            c = row16_sum(c);
+            rs[j] = (lane & 15) == 0 ? c : 0.f;
+        }
+        store_k16<PREC>(gd + I::k_ld() * 64, rs);
+        sb = reduce_q(sb);
+        if (lane == 0) {
+            img[I::OFF_S + 6] = sb;
+            img[I::OFF_S + 7] = 0.f;
+        }
+    }
 #pragma unroll
     for (int net = 0; net < 2; ++net) {
         if constexpr (H == 32) {
@@ -288,7 +333,7 @@ __device__ __forceinline__ void build_image2(float* img, const float* __restrict
     }
     if (lane == 0) {
 #pragma unroll
-        for (int l = 0; l < 4; ++l) {
+        for (int l = 0; l < (LDR ? 3 : 4); ++l) {
             img[I::OFF_S + 2 * l] = l < L ? Sst[l < L ? l : 0][0] : 1.f;
             img[I::OFF_S + 2 * l + 1] = l < L ? Sst[l < L ? l : 0][1] : 1.f;
         }
@@ -362,15 +407,44 @@ __device__ __forceinline__ void coupling_tile2_bf16(const float* img, int lane, 
     }
 }
 
-template <int H, int L, int NT, bool SLOW, int PREC = 0, bool FWD = false>
+// A half of NT tiles as split operands, packed: v[t][0] the hi halves, v[t][1] the lo halves, element 2 m + p = features
+// 16 m + 4 q + 2 p, + 1 -- the order the first layer's MFMAs take them in.
+template <int H, int NT>
+struct Pk2 {
+    unsigned v[NT][2][H / 8];
+};
+// the split of a half that stays live (the input of the first layer walked)
+template <int H, int NT>
+__device__ __forceinline__ void split_half(const f4 (&x)[NT][H / 16], Pk2<H, NT>& o) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int m = 0; m < H / 16; ++m)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const HiLo a = split2r(x[t][m][2 * p], x[t][m][2 * p + 1]);
+                o.v[t][0][2 * m + p] = a.hi;
+                o.v[t][1][2 * m + p] = a.lo;
+            }
+}
+
+// LD = float: ssum2[t] += this lane's share of sum(s) log2(e), one add per feature.  LD = f4 (image with the log-det
+//   row, Img2<H, L, true>): ssum2[t] is an accumulator tile carried through all layers, sum(s) log2(e) of sample
+//   (lane & 15) arrives in element 0 of the lanes with q = 0 (the other rows of the group are zero).
+// xs: the conditioner half already split (by split_half or by the layer before); x itself then only feeds the SLOW form.
+// ys: where this layer leaves the split of its output, the next layer's xs (inverse direction, split-f16 only).
+template <int H, int L, int NT, bool SLOW, int PREC = 0, bool FWD = false, class LD = float>
 __device__ __forceinline__ void coupling_tile2(const float* img, int lane, const f4 (&x)[NT][H / 16], f4 (&y)[NT][H / 16],
-                                               float (&ssum2)[NT]) {
+                                               LD (&ssum2)[NT], const Pk2<H, NT>* xs = nullptr, Pk2<H, NT>* ys = nullptr) {
     static_assert(!(FWD && PREC == 1), "the bf16 experiment covers the inverse direction");
+    constexpr bool LDR = std::is_same<LD, f4>::value;
+    static_assert(LDR || std::is_same<LD, float>::value, "log-det sum: float or accumulator tile");
     if constexpr (PREC == 1) {
+        static_assert(PREC != 1 || !LDR, "the bf16 experiment keeps the add chain");
         coupling_tile2_bf16<H, L, NT>(img, lane, x, y, ssum2);
         return;
     }
-    typedef Img2<H, L> I;
+    typedef Img2<H, L, LDR> I;
     constexpr int HT = I::HT;
 #if TNF2_SCHED == 3 || TNF2_SCHED == 4
     __builtin_amdgcn_sched_barrier(0);  // one scheduling region per layer (without it the group solver ran > 30 min)
@@ -395,6 +469,11 @@ __device__ __forceinline__ void coupling_tile2(const float* img, int lane, const
             h8 xh[NT], xl[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
+                if (xs) {
+                    xh[t] = __builtin_bit_cast(h8, u4{xs->v[t][0][0], xs->v[t][0][1], xs->v[t][0][2], xs->v[t][0][3]});
+                    xl[t] = __builtin_bit_cast(h8, u4{xs->v[t][1][0], xs->v[t][1][1], xs->v[t][1][2], xs->v[t][1][3]});
+                    continue;
+                }
                 const HiLo a = split2r(x[t][0][0], x[t][0][1]), b = split2r(x[t][0][2], x[t][0][3]);
                 const HiLo c = split2r(x[t][1][0], x[t][1][1]), d = split2r(x[t][1][2], x[t][1][3]);
                 xh[t] = __builtin_bit_cast(h8, u4{a.hi, b.hi, c.hi, d.hi});
@@ -415,7 +494,14 @@ __device__ __forceinline__ void coupling_tile2(const float* img, int lane, const
         } else {
             h4 xh[NT], xl[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) split4r(x[t][0], xh[t], xl[t]);
+            for (int t = 0; t < NT; ++t) {
+                if (xs) {
+                    xh[t] = __builtin_bit_cast(h4, u2{xs->v[t][0][0], xs->v[t][0][1]});
+                    xl[t] = __builtin_bit_cast(h4, u2{xs->v[t][1][0], xs->v[t][1][1]});
+                } else {
+                    split4r(x[t][0], xh[t], xl[t]);
+                }
+            }
 #pragma unroll
             for (int net = 0; net < 2; ++net) {
                 const u4 wv = gd[I::k_l0(net) * 64];
@@ -471,6 +557,20 @@ __device__ __forceinline__ void coupling_tile2(const float* img, int lane, const
             for (int net = 0; net < 2; ++net) split4r(sig2s_4(acc[t][net], Sc(l + 1, net)), rh[t][net], rl[t][net]);
     }
     // ---- output layer and the update of the transformed half ----
+    auto ld_add = [&](int t, float s2, bool first) {  // the add chain of the log-det (first: feature 0 of the tile)
+        if constexpr (!LDR) {
+#if TNF2_ABL == 3  // timing experiment only: one log-det add per tile instead of eight
+            if (first)
+#endif
+                ssum2[t] += s2;
+        }
+        (void)first;
+    };
+    if constexpr (LDR) {
+        const u4 wv = gd[I::k_ld() * 64];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) ssum2[t] = contract16(wv, rh[t][1], rl[t][1], ssum2[t]);
+    }
 #pragma unroll
     for (int mo = 0; mo < HT; ++mo) {
         f4 tt[NT], sv[NT];
@@ -489,16 +589,35 @@ __device__ __forceinline__ void coupling_tile2(const float* img, int lane, const
         const f4 ay = *reinterpret_cast<const f4*>(img + I::OFF_A + 16 * mo + 4 * (lane >> 4));
         f4 by = {0.f, 0.f, 0.f, 0.f};
         if constexpr (FWD) by = *reinterpret_cast<const f4*>(img + I::OFF_A + H + 16 * mo + 4 * (lane >> 4));
+        if constexpr (!FWD) {
+            if (ys) {
+                // update and split in one go: u = fma(y, Ay, -t) is dead after the multiply, the remainder of y' goes there
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) {
+                        const int j0 = 2 * p, j1 = 2 * p + 1;
+                        ld_add(t, sv[t][j0], mo == 0 && p == 0);
+                        ld_add(t, sv[t][j1], false);
+                        float u0 = __builtin_fmaf(y[t][mo][j0], ay[j0], -tt[t][j0]);
+                        float u1 = __builtin_fmaf(y[t][mo][j1], ay[j1], -tt[t][j1]);
+                        const float v0 = u0 * __builtin_amdgcn_exp2f(-sv[t][j0]);
+                        const float v1 = u1 * __builtin_amdgcn_exp2f(-sv[t][j1]);
+                        y[t][mo][j0] = v0;
+                        y[t][mo][j1] = v1;
+                        const HiLo a = split2r_into(v0, v1, u0, u1);
+                        ys->v[t][0][2 * mo + p] = a.hi;
+                        ys->v[t][1][2 * mo + p] = a.lo;
+                    }
+                continue;
+            }
+        }
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float s2 = sv[t][j];
-#if TNF2_ABL == 3  // timing experiment only: one log-det add per tile instead of eight
-                if (j == 0 && mo == 0) ssum2[t] += s2;
-#else
-                ssum2[t] += s2;
-#endif
+                ld_add(t, s2, mo == 0 && j == 0);
                 if constexpr (FWD)
                     y[t][mo][j] = __builtin_fmaf(__builtin_fmaf(y[t][mo][j], ay[j], by[j]), __builtin_amdgcn_exp2f(s2), tt[t][j]);
                 else

@@ -67,41 +67,70 @@
 namespace tnf {
 
 
-template <int H, int L>
+template <int H, int L, bool LDR = false>
 __host__ __device__ constexpr int flow2_lds_floats(int nl) {
     // images | fold (nl + 1, 2, D) | fin [A (D) | B (D)] | kappa (nl ints) pad 16 | queue head (4) | red (16) | iv (7 D)
-    return nl * Img2<H, L>::FLOATS + (nl + 1) * 4 * H + 4 * H + ((nl + 3) / 4) * 4 + 4 + 16 + 7 * 2 * H;
+    return nl * Img2<H, L, LDR>::FLOATS + (nl + 1) * 4 * H + 4 * H + ((nl + 3) / 4) * 4 + 4 + 16 + 7 * 2 * H;
 }
 
+// Which instances take the two lean forms of the layer body (TNF2_PSPLIT, TNF2_LDMFMA): the ones that stay inside their
+// register budget with them.  The padded layouts (staging registers) and H = 16 with three layers (168 registers at
+// twelve waves) gain spills and keep the body they had.
+template <int H, int L, bool PAD>
+constexpr bool kLeanBody2 = !PAD && !(H == 16 && L == 3);
+
 // all coupling layers of one group of NT tiles; lo / hi: the two halves of the registers (see f16_tile2.h)
-template <int H, int L, int NT, int SS, bool SLOW, bool FWD = false>
+// LD: the log-det sum, float (add chain) or f4 (accumulator tile of the image's log-det row) -- coupling_tile2
+// PS: layers hand the split of their output on (inverse direction, not the exact re-run)
+template <int H, int L, int NT, int SS, bool SLOW, bool FWD = false, class LD = float, bool PS = false>
 __device__ __forceinline__ void run_layers2(const float* img, int S, int lane, f4 (&lo)[NT][H / 16], f4 (&hi)[NT][H / 16],
-                                            float (&ssum)[NT]) {
-    typedef Img2<H, L> I;
+                                            LD (&ssum)[NT]) {
+    typedef Img2<H, L, std::is_same<LD, f4>::value> I;
     if constexpr (FWD) {  // sampling direction: layer 2 st conditions on the lower half, 2 st + 1 on the upper
         if constexpr (SS > 0 && !SLOW) {
 #pragma unroll
             for (int st = 0; st < SS; ++st) {
-                coupling_tile2<H, L, NT, false, 0, true>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum);
-                coupling_tile2<H, L, NT, false, 0, true>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum);
+                coupling_tile2<H, L, NT, false, 0, true, LD>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum);
+                coupling_tile2<H, L, NT, false, 0, true, LD>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum);
             }
         } else {
             for (int st = 0; st < S; ++st) {
-                coupling_tile2<H, L, NT, SLOW, 0, true>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum);
-                coupling_tile2<H, L, NT, SLOW, 0, true>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum);
+                coupling_tile2<H, L, NT, SLOW, 0, true, LD>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum);
+                coupling_tile2<H, L, NT, SLOW, 0, true, LD>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum);
             }
+        }
+    } else if constexpr (PS && !SLOW) {
+        // every layer hands the split of its output to the next one (the half it transformed is the next conditioner);
+        // the first layer walked gets the split of the loaded half, the last one emits none
+        Pk2<H, NT> pa, pb;
+        split_half<H, NT>(hi, pa);
+        if constexpr (SS > 0) {
+#pragma unroll
+            for (int i = 0; i < SS; ++i) {
+                const int st = SS - 1 - i;
+                coupling_tile2<H, L, NT, false, 0, false, LD>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum, &pa, &pb);
+                coupling_tile2<H, L, NT, false, 0, false, LD>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum, &pb,
+                                                              st > 0 ? &pa : nullptr);
+            }
+        } else {
+            for (int st = S - 1; st > 0; --st) {
+                coupling_tile2<H, L, NT, false, 0, false, LD>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum, &pa, &pb);
+                coupling_tile2<H, L, NT, false, 0, false, LD>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum, &pb, &pa);
+            }
+            coupling_tile2<H, L, NT, false, 0, false, LD>(img + I::FLOATS, lane, hi, lo, ssum, &pa, &pb);
+            coupling_tile2<H, L, NT, false, 0, false, LD>(img, lane, lo, hi, ssum, &pb);
         }
     } else if constexpr (SS > 0 && !SLOW) {
 #pragma unroll
         for (int i = 0; i < SS; ++i) {
             const int st = SS - 1 - i;
-            coupling_tile2<H, L, NT, false>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum);
-            coupling_tile2<H, L, NT, false>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum);
+            coupling_tile2<H, L, NT, false, 0, false, LD>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum);
+            coupling_tile2<H, L, NT, false, 0, false, LD>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum);
         }
     } else {
         for (int st = S - 1; st >= 0; --st) {
-            coupling_tile2<H, L, NT, SLOW>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum);
-            coupling_tile2<H, L, NT, SLOW>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum);
+            coupling_tile2<H, L, NT, SLOW, 0, false, LD>(img + (2 * st + 1) * I::FLOATS, lane, hi, lo, ssum);
+            coupling_tile2<H, L, NT, SLOW, 0, false, LD>(img + (2 * st) * I::FLOATS, lane, lo, hi, ssum);
         }
     }
 }
@@ -121,12 +150,15 @@ __device__ __forceinline__ int pad_feature(int pf, int H, int h, int Dr) {  // p
     return pf - H < Dr - h ? h + pf - H : -1;
 }
 
-template <int H, int L, int NT, int NWAVES, int SS = 0, bool FWD = false, bool PAD = false>
+// LDR = true (TNF2_LDMFMA builds only): the images carry the log-det row (Img2<H, L, true>, 1 KB more per layer) and the
+// sum of s comes off the matrix pipe; the launcher picks it wherever the larger images fit.
+template <int H, int L, int NT, int NWAVES, int SS = 0, bool FWD = false, bool PAD = false, bool LDR = false>
 __global__ void __launch_bounds__(NWAVES * 64)
 flow_fused2_kernel(Flow2Args a) {
     constexpr int D = 2 * H;
     constexpr int HT = H / 16;
-    typedef Img2<H, L> I;
+    typedef Img2<H, L, LDR> I;
+    typedef typename std::conditional<LDR, f4, float>::type LD;  // a tile's log-det sum: accumulator tile / this lane's share
     const int Dr = PAD ? a.Dr : D;  // real row width (global memory); D: the register / LDS layout
     const int hr = Dr / 2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -208,15 +240,16 @@ flow_fused2_kernel(Flow2Args a) {
             // transformed half still owes from two layers back slot c-1 (slot 0 = identity, so c = 1 is regular)
             const float sc_prev = c > 0 ? pow2i(kap[c - 1]) : 1.f;
             const float sig_next = c < nl - 1 ? pow2i(-kap[c + 1]) : 1.f;
-            build_image2<H, L, 0, true>(img + c * I::FLOATS, pl, a.U, lane, fold + c * 2 * D,
-                                        c > 0 ? fold + (c - 1) * 2 * D : nullptr, c, sc_in, sc_prev, sig_next, d_cond(c),
-                                        d_tran(c));
+            build_image2<H, L, 0, true, LDR>(img + c * I::FLOATS, pl, a.U, lane, fold + c * 2 * D,
+                                             c > 0 ? fold + (c - 1) * 2 * D : nullptr, c, sc_in, sc_prev, sig_next, d_cond(c),
+                                             d_tran(c));
         } else {
             const bool first = (c == nl - 1), last = (c == 0);
             const float sc_prev = first ? 1.f : pow2i(kap[c + 1]);
             const float sig_next = last ? 1.f : pow2i(-kap[c - 1]);
-            build_image2<H, L>(img + c * I::FLOATS, pl, a.U, lane, fold + c * 2 * D,
-                               first ? nullptr : fold + (c + 1) * 2 * D, c, sc_in, sc_prev, sig_next, d_cond(c), d_tran(c));
+            build_image2<H, L, 0, false, LDR>(img + c * I::FLOATS, pl, a.U, lane, fold + c * 2 * D,
+                                              first ? nullptr : fold + (c + 1) * 2 * D, c, sc_in, sc_prev, sig_next, d_cond(c),
+                                              d_tran(c));
         }
     }
     if constexpr (FWD) {
@@ -251,6 +284,23 @@ flow_fused2_kernel(Flow2Args a) {
     float ldc = 0.f;
 #pragma unroll
     for (int w = 0; w < NWAVES; ++w) ldc += red[w];
+    // log-det sum of a tile: where it starts (LDR: the s biases of all layers, which the add chain met inside s) and
+    // how it is read (LDR: row 0 of the accumulator tile, valid in the lanes with q = 0 -- the ones that store)
+    float sb_all = 0.f;
+    if constexpr (LDR)
+        for (int c = 0; c < nl; ++c) sb_all += img[c * I::FLOATS + I::OFF_S + 6];
+    auto ld_zero = [&]() -> LD {
+        if constexpr (LDR) return f4{sb_all, 0.f, 0.f, 0.f};
+        else return 0.f;
+    };
+    auto ld_raw = [&](const LD& v) -> float {
+        if constexpr (LDR) return v[0];
+        else return v;
+    };
+    auto ld_sum = [&](const LD& v) -> float {
+        if constexpr (LDR) return v[0];
+        else return reduce_q(v);
+    };
 
     const int64_t ngroups = (a.N + 16 * NT - 1) / (16 * NT);
     const int64_t per_block = (ngroups + gridDim.x - 1) / gridDim.x;
@@ -397,11 +447,12 @@ flow_fused2_kernel(Flow2Args a) {
         const int64_t nxt = g_lo + __builtin_amdgcn_readfirstlane(nxt_off);
         const bool has_next = nxt < g_hi;
         f4 lo[NT][HT], hi[NT][HT];
-        float ssum[NT], ssup[NT];  // ssup: log-det of the fused support layer (natural log, this lane's features)
+        LD ssum[NT];
+        float ssup[NT];  // ssup: log-det of the fused support layer (natural log, this lane's features)
         if constexpr (PAD) unstage(nraw, lo, hi);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            ssum[t] = 0.f;
+            ssum[t] = ld_zero();
             ssup[t] = 0.f;
             if constexpr (!PAD)
 #pragma unroll
@@ -432,22 +483,22 @@ flow_fused2_kernel(Flow2Args a) {
             if constexpr (PAD) load_raw(nxt, nraw);
             else load_group(nxt, nlo, nhi);
         }
-        run_layers2<H, L, NT, SS, false, FWD>(img, a.S, lane, lo, hi, ssum);
+        run_layers2<H, L, NT, SS, false, FWD, LD, TNF2_PSPLIT && kLeanBody2<H, L, PAD>>(img, a.S, lane, lo, hi, ssum);
         // an input beyond the f16 range of its (scaled) operand turned into NaN and reached the log-det sum:
         // re-run this group with exact first-layer contractions (also taken, harmlessly, by genuine NaN inputs)
-        float chk = ssum[0];
+        float chk = ld_raw(ssum[0]);
 #pragma unroll
-        for (int t = 1; t < NT; ++t) chk += ssum[t];
+        for (int t = 1; t < NT; ++t) chk += ld_raw(ssum[t]);
         if (__builtin_expect(__any(chk != chk), 0)) {
             if constexpr (PAD) load_frag(grp, lo, hi);
             else load_group(grp, lo, hi);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                ssum[t] = 0.f;
+                ssum[t] = ld_zero();
                 ssup[t] = 0.f;
             }
             enter(lo, hi, ssup);
-            run_layers2<H, L, NT, 0, true, FWD>(img, a.S, lane, lo, hi, ssum);
+            run_layers2<H, L, NT, 0, true, FWD, LD>(img, a.S, lane, lo, hi, ssum);
             if (a.slow_count && lane == 0) atomicAdd(a.slow_count, 1u);
         }
         leave(lo, hi, ssup);
@@ -455,7 +506,7 @@ flow_fused2_kernel(Flow2Args a) {
         for (int t = 0; t < NT; ++t) {
             const int64_t row = (grp * NT + t) * 16 + s;
             const bool row_ok = row < a.N;
-            const float ld_tot = __builtin_fmaf(reduce_q(ssum[t]), kLn2, ldc) + (has_iv ? reduce_q(ssup[t]) : 0.f);
+            const float ld_tot = __builtin_fmaf(ld_sum(ssum[t]), kLn2, ldc) + (has_iv ? reduce_q(ssup[t]) : 0.f);
             if (!FWD && lpo) {
                 float sq = 0.f;
 #pragma unroll
@@ -1127,9 +1178,9 @@ flow_range2_kernel(Range2Args ra) {
     }
 }
 
-template <int H, int L>
+template <int H, int L, bool LDR = false>
 static size_t flow2_lds_bytes(int S) {
-    return (size_t)flow2_lds_floats<H, L>(2 * S) * sizeof(float);
+    return (size_t)flow2_lds_floats<H, L, LDR>(2 * S) * sizeof(float);
 }
 
 static size_t flow2_lds_bytes_rt(int D, int S, int L) {
@@ -1141,7 +1192,9 @@ bool flow_fused2_supported(int D, int S, int L, int U) {
     return flow2_lds_bytes_rt(D, S, L) <= 160 * 1024;
 }
 
-template <int H, int L, int NT, int NW, int SS, bool FWD, bool PAD = false>
+// LDR: the images with the log-det row -- the inverse pass wherever they fit beside everything the launch would have
+// had in LDS without them (what is supported, and whether the rows are staged, never depends on it)
+template <int H, int L, int NT, int NW, int SS, bool FWD, bool PAD = false, bool LDR = false>
 static int launch2_t(const Flow2Args& a, int64_t M, hipStream_t st) {
     size_t smem = flow2_lds_bytes<H, L>(a.S);
     Flow2Args b = a;
@@ -1149,9 +1202,15 @@ static int launch2_t(const Flow2Args& a, int64_t M, hipStream_t st) {
     const size_t stage_bytes = (size_t)NW * 16 * 2 * H * sizeof(float);
     b.stage_out = (!PAD && H == 32 && a.z_out != nullptr && smem + stage_bytes <= 160 * 1024 && TNF2_FUSED_STAGE) ? 1 : 0;
     if (b.stage_out || PAD) smem += stage_bytes;  // PAD: every row goes in and out through the staging tiles
+    if constexpr (LDR || (TNF2_LDMFMA && kLeanBody2<H, L, PAD> && !FWD)) {
+        const size_t ldr_bytes = flow2_lds_bytes<H, L, true>(a.S) - flow2_lds_bytes<H, L, false>(a.S);
+        if constexpr (LDR) smem += ldr_bytes;
+        else if (smem + ldr_bytes <= 160 * 1024) return launch2_t<H, L, NT, NW, SS, FWD, PAD, true>(a, M, st);
+    }
     // one workgroup per CU (LDS-limited), persistent over its groups
     const int64_t bx = persistent_bx_ceil((a.N + 16 * NT - 1) / (16 * NT), NW, 256, M);
-    return launch_lds("flow_fused2", flow_fused2_kernel<H, L, NT, NW, SS, FWD, PAD>, grid_xm(bx, M), dim3(NW * 64), smem, st, b);
+    return launch_lds("flow_fused2", flow_fused2_kernel<H, L, NT, NW, SS, FWD, PAD, LDR>, grid_xm(bx, M), dim3(NW * 64), smem, st,
+                      b);
 }
 
 template <int H, int L, bool PAD = false>

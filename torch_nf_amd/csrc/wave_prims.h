@@ -85,6 +85,18 @@ __device__ __forceinline__ HiLo split2r(float v0, float v1) {
     split_remainder(v0, v1, hb);
     return HiLo{hb, __builtin_bit_cast(unsigned, __builtin_convertvector(f2{v0, v1}, h2))};
 }
+// The same split of v0, v1 with the remainders written over d0, d1 instead: two DEAD values that an ordinary VALU
+// instruction produced after the MFMAs (clause (b) of the rule; v0, v1 are ordinary VALU results, clause (a)), so a v
+// that stays live is not copied first.  The instructions and their inputs are split2r's: the same bits.
+__device__ __forceinline__ HiLo split2r_into(float v0, float v1, float& d0, float& d1) {
+    const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{v0, v1}, h2));
+#if TNF_SPLIT_RNE_NO_REMAINDER
+    return HiLo{hb, hb};
+#endif
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(d0) : "v"(hb), "v"(v0));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(d1) : "v"(hb), "v"(v1));
+    return HiLo{hb, __builtin_bit_cast(unsigned, __builtin_convertvector(f2{d0, d1}, h2))};
+}
 // (vector elements cannot bind to references, hence the macro)
 #define split2(V0, V1, HI, LO)                \
     do {                                      \
