@@ -9,11 +9,12 @@ reference's import names so existing `import torch_nf.bijectors` code picks them
 import sys
 
 from . import _lib  # noqa: F401  (fails loudly if libtnf_hip.so is missing)
-from . import (bijectors, conditional_density_estimator, density_estimator, error_formatters, exponential_families, graphs,
-               lfi, systems)
+from . import (bijectors, conditional_density_estimator, density_estimator, efn, error_formatters, exponential_families,
+               graphs, lfi, systems)
 from .bijectors import MAF, ToInterval, ToSimplex, Affine, BatchNorm, Bijector, RealNVP
 from .conditional_density_estimator import ConditionalDensityEstimator
 from .density_estimator import DensityEstimator, MoG, NormFlow
+from .efn import train_efn
 from .exponential_families import MVN, Dirichlet, ExponentialFamily
 from .lfi import ABC_MCMC, ABC_SMC, train_nde
 from .systems import GaussianProposal, HebbLearn, Mat
@@ -21,7 +22,8 @@ from .systems import GaussianProposal, HebbLearn, Mat
 __version__ = "0.1.0"
 __all__ = ["Bijector", "RealNVP", "MAF", "ToInterval", "ToSimplex", "Affine", "BatchNorm", "DensityEstimator", "NormFlow", "MoG",
            "ConditionalDensityEstimator", "ExponentialFamily", "MVN", "Dirichlet", "exponential_families",
-           "ABC_SMC", "ABC_MCMC", "GaussianProposal", "Mat", "HebbLearn", "train_nde", "install_as_torch_nf"]
+           "ABC_SMC", "ABC_MCMC", "GaussianProposal", "Mat", "HebbLearn", "train_nde", "train_efn",
+           "install_as_torch_nf"]
 
 
 def install_as_torch_nf():
@@ -29,6 +31,6 @@ def install_as_torch_nf():
     this = sys.modules[__name__]
     sys.modules.setdefault("torch_nf", this)
     for name in ("bijectors", "density_estimator", "conditional_density_estimator", "error_formatters", "exponential_families", "lfi",
-                 "systems"):
+                 "systems", "efn"):
         sys.modules["torch_nf." + name] = getattr(this, name)
     return this

@@ -34,6 +34,8 @@ ABC_COUNT_SMC, ABC_COUNT_PROPOSE, ABC_COUNT_NOISE = 0, 1, 2  # tnf_abc_launch_co
 ABC_MAX_D, ABC_MAX_SMC_D, ABC_MAX_TRIALS = 21, 6, 1 << 24  # include/tnf_abc.h
 HEBB_COUNT_SIM, HEBB_COUNT_NOISE = 0, 1  # tnf_hebb_launch_count
 HEBB_MAX_N = 64  # include/tnf_hebb.h
+EFN_COUNT_PRIOR, EFN_COUNT_NOISE, EFN_COUNT_KL = 0, 1, 2  # tnf_efn_launch_count
+EFN_MAX_D, EFN_MAX_DF = 64, 1024  # include/tnf_efn.h
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
@@ -190,6 +192,17 @@ HEBB_SIGNATURES = {
     "tnf_hebb_noise_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
 }
 
+# the EFN training loop's prior and KL kernels, declared in include/tnf_efn.h: a fifth table (tests/test_efn_host.py)
+EFN_SIGNATURES = {
+    "tnf_efn_supported": (ctypes.c_int, [_i32, _i32]),
+    "tnf_efn_launch_count": (_i64, [_i32]),
+    "tnf_efn_prior_num_noise": (_i64, [_i32, _i32, _i32]),
+    "tnf_efn_prior_noise_f32": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _vp]),
+    "tnf_efn_prior_f32": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i64, _i64, _i64, _i64, _vp]),
+    "tnf_efn_kl_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32]),
+    "tnf_efn_kl_f32": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -199,7 +212,7 @@ def _load():
             "There is no non-HIP fallback." % LIB_PATH
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES):
+    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

@@ -5,7 +5,9 @@ natural parameter (a trailing 1 where the log base measure depends on z) and `T`
 log h(z) appended likewise.  The parameter conversions, the prior draws and KL are small host-side numpy, as in the
 reference; the two tensor operations of an EFN objective -- T(z) and the contraction eta . T(z) -- run in HIP kernels
 (ops.ef_suffstats / ops.ef_dot).  `eta_dot_T` and `efn_loss` are additions: they evaluate the loss term without ever
-forming the (M, N, D_eta) tensor T(z).
+forming the (M, N, D_eta) tensor T(z).  `sample_eta_device` and `KL_device` are additions too: the prior draw and the KL
+diagnostic as HIP kernels (efn_ops, include/tnf_efn.h), float32 on the device and without a host synchronisation, so that
+efn.train_efn keeps a whole iteration on the device; the host `sample_eta` / `KL` stay what they were.
 
 One deliberate difference: `MVN.sample_eta` draws its inverse-Wishart covariances with numpy alone (Bartlett factor),
 not with scipy, which this package does not depend on.  It consumes np.random's global state, so np.random.seed
@@ -67,6 +69,24 @@ class ExponentialFamily(object):
     def sample_eta(self, N):
         """Draw N natural parameters from the family's prior -> np.ndarray (N, D_eta)."""
         raise NotImplementedError()
+
+    def sample_eta_device(self, N, seed=0, t=0, t_dev=None):
+        """`sample_eta` on the device -> float32 tensor (N, D_eta): draw t of the counter-based stream keyed by `seed`
+        (include/tnf_efn.h), NOT np.random's.  t_dev: one int64 on the device read in place of t."""
+        raise NotImplementedError()
+
+    def KL_device(self, z, log_prob, eta):
+        """`KL` on the device -> float32 tensor (M,): mean_n(log_prob[m, n] - log p(z[m, n]; eta[m])) by the kernels of
+        include/tnf_efn.h.  z (M, N, D) float32, log_prob (M, N) float32 or float64, eta (M, D_eta); no host
+        synchronisation.  A context whose eta is not a valid natural parameter gets NaN where `KL` would raise."""
+        if self._family is None:
+            raise NotImplementedError()
+        from . import efn_ops
+
+        self._check_z(z)
+        if not torch.is_tensor(eta):
+            eta = torch.as_tensor(np.asarray(eta))
+        return efn_ops.efn_kl(self._family, z.detach(), log_prob.detach(), eta.detach().float())
 
     def mu_to_eta(self, mu):
         """Mean parameterisation -> natural parameters (N, D_eta)."""
@@ -137,6 +157,13 @@ class MVN(ExponentialFamily):
         Sigma = _inv_wishart(N, self.D, iw_df_fac * self.D)
         return self.mu_to_eta(mu, Sigma)
 
+    def sample_eta_device(self, N=50, sigma_mu=1., iw_df_fac=5, seed=0, t=0, t_dev=None):
+        """The prior of `sample_eta` drawn on the device: the precision W ~ Wishart(df, I / df) is built from its Bartlett
+        factor and used as it is (`sample_eta` inverts it into Sigma and `mu_to_eta` inverts Sigma again)."""
+        from . import efn_ops
+
+        return efn_ops.efn_prior(self._family, self.D, N, iw_df_fac=iw_df_fac, sigma_mu=sigma_mu, seed=seed, t=t, t_dev=t_dev)
+
     def T(self, z):
         return self._T(z)
 
@@ -195,6 +222,12 @@ class Dirichlet(ExponentialFamily):
     def sample_eta(self, N=50, lb=0.5, ub=2.):
         """alpha_i ~ U[lb, ub] -> eta = [alpha | 1] (N, D_eta)."""
         return self.mu_to_eta(np.random.uniform(lb, ub, (N, self.D)))
+
+    def sample_eta_device(self, N=50, lb=0.5, ub=2., seed=0, t=0, t_dev=None):
+        """The prior of `sample_eta` drawn on the device."""
+        from . import efn_ops
+
+        return efn_ops.efn_prior(self._family, self.D, N, lb=lb, ub=ub, seed=seed, t=t, t_dev=t_dev)
 
     def T(self, z):
         return self._T(z)
