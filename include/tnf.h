@@ -634,4 +634,5 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
 #include "tnf_abc.h"
 #include "tnf_hebb.h"
 #include "tnf_efn.h"
+#include "tnf_padtrain.h"
 #endif /* TNF_H */

@@ -36,6 +36,8 @@ HEBB_COUNT_SIM, HEBB_COUNT_NOISE = 0, 1  # tnf_hebb_launch_count
 HEBB_MAX_N = 64  # include/tnf_hebb.h
 EFN_COUNT_PRIOR, EFN_COUNT_NOISE, EFN_COUNT_KL = 0, 1, 2  # tnf_efn_launch_count
 EFN_MAX_D, EFN_MAX_DF = 64, 1024  # include/tnf_efn.h
+PADTRAIN_COUNT_EMBED_ROWS, PADTRAIN_COUNT_GATHER_ROWS, PADTRAIN_COUNT_EMBED_PARAMS = 0, 1, 2  # tnf_padtrain_launch_count
+PADTRAIN_COUNT_GATHER_PARAMS, PADTRAIN_COUNT_BWD = 3, 4
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
@@ -203,6 +205,23 @@ EFN_SIGNATURES = {
     "tnf_efn_kl_f32": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _i64, _vp]),
 }
 
+# training a coupling flow of any width 2 .. 63 through the reversible backward at the embedded width, declared in
+# include/tnf_padtrain.h: a sixth table (tests/test_padded_train_host.py)
+PADTRAIN_SIGNATURES = {
+    "tnf_flow_padded_train_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "tnf_flow_padded_width": (ctypes.c_int, [_i32]),
+    "tnf_flow_padded_embed_index": (_i64, [_i32, _i32, _i32, _i32, _i64]),
+    "tnf_padtrain_launch_count": (_i64, [_i32]),
+    "tnf_flow_padded_embed_rows_f32": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "tnf_flow_padded_gather_rows_f32": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "tnf_flow_padded_embed_params_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64,
+                                                        _vp]),
+    "tnf_flow_padded_gather_params_f32": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp]),
+    "tnf_flow_padded_train_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "tnf_flow_padded_log_prob_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
+                                                        _i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -212,7 +231,7 @@ def _load():
             "There is no non-HIP fallback." % LIB_PATH
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES):
+    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

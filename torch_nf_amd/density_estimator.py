@@ -32,11 +32,17 @@ only the per-bijector composition differentiates through them); "not few" = not 
   train_reversible  log_prob             coupling, float32, const stats, 3-d, M_z >= M_p,            flow_log_prob_train
                                          reversible_training, flow_train_rev_supported               (reversible=True)
   train_layers      log_prob             the same, flow_train_supported                              (reversible=False)
+  train_padded      log_prob             padded_training (default off), coupling, float32, const     padtrain_ops.flow_padded_
+                                         stats, 3-d, M_z >= M_p, one parameter row or 32 samples     log_prob_train
+                                         per row, fusion AUTO or FLOW, flow_padded_train_supported
+                                         (2 <= D <= 63 but 32: asked after train_reversible, whose
+                                         widths it excludes, and before train_layers)
   bijectors         all                  everything else: the reference's loop, one kernel per       coupling, maf, affine,
                                          bijector                                                    bn_apply, bn_batch_forward
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
-a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded` and the per-layer chain do not.
+a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded` and the per-layer
+chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
 Sampling: the base density is evaluated first (base_log_density_f64), except that `padded` and the whole-flow `fused`
@@ -47,7 +53,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, padtrain_ops
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -290,12 +296,17 @@ class NormFlow(DensityEstimator):
 
     def _train_path(self, z, params, stats_graph=None):
         """The fused training pair of a coupling log_prob: "reversible" (whole-flow forward, one-kernel backward from
-        z0), "layers" (one fused kernel per layer each way, for the shapes that pair does not cover) or None."""
+        z0), "padded" (the same pair for 2 <= D <= 63 but 32: padded whole-flow forward, the one-kernel backward at the
+        embedded width 2H; only with the switch `padded_training` on, and the fusion setting AUTO or FLOW as for the
+        `padded` family), "layers" (one fused kernel per layer each way, for the shapes those do not cover) or None."""
         if self._stats_in_graph() if stats_graph is None else stats_graph:
             return None  # the fused training pairs treat the statistics as constants
         shape = (z.size(0), params.size(0), z.size(1), self.D, self.num_stages, self.num_layers, self.num_units)
         if getattr(self, "reversible_training", True) and ops.flow_train_rev_supported(*shape):
             return "reversible"
+        if (getattr(self, "padded_training", False) and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
+                and padtrain_ops.flow_padded_train_supported(*shape)):
+            return "padded"
         if ops.flow_train_supported(*shape):
             return "layers"
         return None
@@ -499,6 +510,8 @@ class NormFlow(DensityEstimator):
         elif family == "ar_train":
             masks, mean, alpha, D, L, U = self._ar_args()
             log_q = ops.ar_flow_log_prob_train(z, params, masks, mean, alpha, consts, D, L, U)
+        elif family == "train_padded":  # ... at 2 <= D <= 63 but 32: the reversible pair at the embedded width
+            log_q = padtrain_ops.flow_padded_log_prob_train(z, params, *self._flow_args())
         elif family != "bijectors":  # training with the BatchNorm statistics constant, one of the two fused pairs
             log_q = ops.flow_log_prob_train(z, params, *self._flow_args(), reversible=family == "train_reversible")
         else:
