@@ -635,4 +635,5 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
 #include "tnf_hebb.h"
 #include "tnf_efn.h"
 #include "tnf_padtrain.h"
+#include "tnf_padbatch.h" /* sampling with fresh batch statistics at any D <= 63: a header and a table of its own */
 #endif /* TNF_H */

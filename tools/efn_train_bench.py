@@ -14,8 +14,10 @@ by one on the host clock between two synchronisations, after a settling run of 0
 alone, timed with events: the KL call is its three launches (prepare, stream, reduce) together, so the fraction of the
 HBM roof it gives for the stream kernel at 4 (D + 1) B per sample is a lower bound.  `--kernels-only` runs just the KL calls
 at the three large shapes, one kernel name per shape: the run to put under `rocprofv3 --kernel-trace --stats` for the
-stream kernels' own times.
-Usage: python tools/efn_train_bench.py [--kernels-only]"""
+stream kernels' own times.  `--padded-batch-forward` turns NormFlow.padded_batch_forward on for every flow, so that the
+notebook's width (D = 4) samples through the one-node chain at the embedded width (include/tnf_padbatch.h), and runs the
+iteration forms only; compare with a run without it.
+Usage: python tools/efn_train_bench.py [--kernels-only | --padded-batch-forward]"""
 import os
 import sys
 import time
@@ -169,9 +171,14 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["--kernels-only"]:
         kernels_alone(large_only=True)
         sys.exit(0)
+    padded = sys.argv[1:] == ["--padded-batch-forward"]
+    if padded:
+        tnf.NormFlow.padded_batch_forward = True
+        print("NormFlow.padded_batch_forward = True")
     iteration_forms("notebook: Dirichlet(5), NormFlow(4, True, 'coupling', 1, 1, 15, ToSimplex(4)), hidden [100]",
                     tnf.Dirichlet(5), lambda: tnf.NormFlow(4, True, "coupling", 1, 1, 15, support_layer=tnf.ToSimplex(4)),
                     [100], 100, 100)
     iteration_forms("MVN(64), NormFlow(64, True, 'coupling', 4, 2, 15), hidden [100]", tnf.MVN(64),
                     lambda: tnf.NormFlow(64, True, "coupling", 4, 2, 15), [100], 64, 1024)
-    kernels_alone()
+    if not padded:
+        kernels_alone()

@@ -222,6 +222,24 @@ PADTRAIN_SIGNATURES = {
                                                         _i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp]),
 }
 
+# sampling a coupling flow of any width 2 .. 63 with fresh batch statistics in one call (the batch-statistics chains at
+# the embedded width with a pad-aware fold), declared in include/tnf_padbatch.h: a seventh table
+# (tests/test_padded_batch_host.py)
+PADBATCH_SIGNATURES = {
+    "tnf_flow_padded_batch_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "tnf_padbatch_launch_count": (_i64, [_i32]),
+    "tnf_flow_padded_batch_fold_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _i32, _i32, _f32,
+                                                      _vp]),
+    "tnf_flow_padded_batch_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "tnf_flow_padded_forward_batch_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32,
+                                                         _i32, _i64, _f32, _vp, _i64, _vp]),
+    "tnf_flow_padded_batch_train_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "tnf_flow_padded_forward_train_fwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32,
+                                                             _i32, _i32, _i32, _i64, _f32, _vp, _i64, _vp]),
+    "tnf_flow_padded_forward_train_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                                             _i64, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -231,7 +249,8 @@ def _load():
             "There is no non-HIP fallback." % LIB_PATH
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES):
+    for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
+                  PADBATCH_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

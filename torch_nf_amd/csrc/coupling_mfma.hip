@@ -612,10 +612,15 @@ int flow_forward_batch_layer(int c, const float* z_in, const float* params, floa
 }
 
 int flow_forward_batch_fold(int c, const float* params, const double* moments, float* bn_mean_out, float* bn_alpha_out,
-                            int64_t Mp, int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st) {
+                            int64_t Mp, int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st,
+                            int real_D) {
     const FbWs w = fb_ws(ws, Mp, D);
     const FlowLayout fl = flow_layout(D, S, L, U);
     if (!moments) moments = w.moments;
+    if (real_D)  // an embedded flow: BatchNorm over a padded column is not the identity (flow_pad_batch.hip)
+        return launch_pad_finalize_fold(params, pstride, (int64_t)(c >> 1) * fl.stage + fl.p_up + fl.p_low, moments, eps,
+                                        bn_mean_out + (int64_t)c * D, bn_alpha_out + (int64_t)c * D, w.fold, w.ldc, Mp, D,
+                                        real_D, c & 1, c == 0, st);
     hipLaunchKernelGGL(flow_batch_finalize_fold_kernel, dim3((unsigned)Mp), dim3(256), 0, st, params, pstride,
                        (int64_t)(c >> 1) * fl.stage + fl.p_up + fl.p_low, moments, eps, bn_mean_out + (int64_t)c * D,
                        bn_alpha_out + (int64_t)c * D, w.fold, w.ldc, D, c & 1, c == 0);
@@ -805,7 +810,8 @@ int64_t flow_forward_train_workspace(int64_t M, int64_t Mp, int64_t N, int D, in
 
 int launch_flow_forward_train_fwd(const float* omega, const float* params, float* z_out, float* sum_log_det, float* states,
                                   float* folds, float* bn_mean_out, float* bn_alpha_out, int64_t M, int64_t Mp, int64_t N,
-                                  int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st) {
+                                  int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st,
+                                  int real_D) {
     if (!mfma_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "flow_forward_train: D=%d L=%d U=%d", D, L, U);
     if (N <= 0) return TNF_OK;
     const FbWs w = fb_ws(ws, Mp, D);
@@ -832,9 +838,17 @@ int launch_flow_forward_train_fwd(const float* omega, const float* params, float
         if (rc) return rc;
         rc = launch_bn_moments(states + (int64_t)c * plane, sums, M * N, D, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(flow_batch_finalize_fold_kernel, dim3((unsigned)Mp), dim3(256), 0, st, params, pstride,
-                           (int64_t)(c >> 1) * fl.stage + fl.p_up + fl.p_low, sums, eps, bn_mean_out + (int64_t)c * D,
-                           bn_alpha_out + (int64_t)c * D, folds + (int64_t)c * Mp * 2 * D, ldc, D, c & 1, c == 0);
+        const int64_t aff = (int64_t)(c >> 1) * fl.stage + fl.p_up + fl.p_low;
+        if (real_D) {  // an embedded flow: the pad-aware fold (flow_pad_batch.hip)
+            rc = launch_pad_finalize_fold(params, pstride, aff, sums, eps, bn_mean_out + (int64_t)c * D,
+                                          bn_alpha_out + (int64_t)c * D, folds + (int64_t)c * Mp * 2 * D, ldc, Mp, D, real_D,
+                                          c & 1, c == 0, st);
+            if (rc) return rc;
+            continue;
+        }
+        hipLaunchKernelGGL(flow_batch_finalize_fold_kernel, dim3((unsigned)Mp), dim3(256), 0, st, params, pstride, aff, sums,
+                           eps, bn_mean_out + (int64_t)c * D, bn_alpha_out + (int64_t)c * D, folds + (int64_t)c * Mp * 2 * D,
+                           ldc, D, c & 1, c == 0);
     }
     int64_t nb = (N * D / 4 + 255) / 256;
     if (nb > 2048) nb = 2048;

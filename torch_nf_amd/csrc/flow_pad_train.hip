@@ -116,8 +116,8 @@ static unsigned rows_grid(int64_t R, int H) {
     return (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));  // grid-stride beyond 32 workgroups per CU
 }
 
-// the launchers: arguments checked by the entries
-static int launch_embed_rows(const float* rows, float* out, int64_t R, int D, hipStream_t st) {
+// the launchers: arguments checked by the entries (tnf_common.h: flow_pad_batch.hip composes them too)
+int launch_embed_rows(const float* rows, float* out, int64_t R, int D, hipStream_t st) {
     const int H = padtrain_half(D);
     padtrain_count(TNF_PADTRAIN_COUNT_EMBED_ROWS);
     if (H == 16) hipLaunchKernelGGL(padtrain_embed_rows_kernel<16>, dim3(rows_grid(R, H)), dim3(256), 0, st, rows, out, R, D);
@@ -125,7 +125,7 @@ static int launch_embed_rows(const float* rows, float* out, int64_t R, int D, hi
     return check_launch("flow_padded_embed_rows");
 }
 
-static int launch_gather_rows(const float* rows, float* out, int64_t R, int D, hipStream_t st) {
+int launch_gather_rows(const float* rows, float* out, int64_t R, int D, hipStream_t st) {
     const int H = padtrain_half(D);
     padtrain_count(TNF_PADTRAIN_COUNT_GATHER_ROWS);
     if (H == 16) hipLaunchKernelGGL(padtrain_gather_rows_kernel<16>, dim3(rows_grid(R, H)), dim3(256), 0, st, rows, out, R, D);
@@ -133,20 +133,21 @@ static int launch_gather_rows(const float* rows, float* out, int64_t R, int D, h
     return check_launch("flow_padded_gather_rows");
 }
 
-static int launch_embed_params(const float* params, const float* bn_mean, const float* bn_alpha, float* params_out,
-                               float* bn_mean_out, float* bn_alpha_out, int64_t Mp, int D, int S, int L, int U,
-                               int64_t pstride, hipStream_t st) {
+int launch_embed_params(const float* params, const float* bn_mean, const float* bn_alpha, float* params_out,
+                        float* bn_mean_out, float* bn_alpha_out, int64_t Mp, int D, int S, int L, int U, int64_t pstride,
+                        hipStream_t st) {
     const int H = padtrain_half(D);
-    PadParamArgs a{params, bn_mean, bn_alpha, params_out, bn_mean_out, bn_alpha_out, pstride, D, H, S, L, U,
+    const int Ss = bn_mean ? S : 0;  // bn_mean == NULL: the parameter rows alone (no statistics block, none is read)
+    PadParamArgs a{params, bn_mean, bn_alpha, params_out, bn_mean_out, bn_alpha_out, pstride, D, H, Ss, L, U,
                    flow_layout(D, S, L, U), flow_layout(2 * H, S, L, U)};
-    const int64_t threads = a.fr.total + (int64_t)2 * 2 * S * 2 * H;
+    const int64_t threads = a.fr.total + (int64_t)2 * 2 * Ss * 2 * H;
     padtrain_count(TNF_PADTRAIN_COUNT_EMBED_PARAMS);
     hipLaunchKernelGGL(padtrain_embed_params_kernel, grid_xm((threads + 255) / 256, Mp), dim3(256), 0, st, a);
     return check_launch("flow_padded_embed_params");
 }
 
-static int launch_gather_params(const float* g, float* g_out, int64_t Mp, int D, int S, int L, int U, int64_t gpstride,
-                                hipStream_t st) {
+int launch_gather_params(const float* g, float* g_out, int64_t Mp, int D, int S, int L, int U, int64_t gpstride,
+                         hipStream_t st) {
     const int H = padtrain_half(D);
     const FlowLayout fr = flow_layout(D, S, L, U), fe = flow_layout(2 * H, S, L, U);
     padtrain_count(TNF_PADTRAIN_COUNT_GATHER_PARAMS);

@@ -226,8 +226,11 @@ int flow_forward_batch_begin(const float* params, int64_t Mp, int D, int S, int 
 int flow_forward_batch_layer(int c, const float* z_in, const float* params, float* z_out, float* sum_log_det,
                              double* moments, int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U, int64_t pstride,
                              void* ws, hipStream_t st);
+// real_D != 0 (here and in launch_flow_forward_train_fwd): the rows are a flow of width real_D embedded at width D
+// (padtrain_map.h); the fold is then the pad-aware one of flow_pad_batch.hip
 int flow_forward_batch_fold(int c, const float* params, const double* moments, float* bn_mean_out, float* bn_alpha_out,
-                            int64_t Mp, int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st);
+                            int64_t Mp, int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st,
+                            int real_D = 0);
 int flow_forward_batch_end(float* z_out, float* sum_log_det, int64_t M, int64_t Mp, int64_t N, int D, void* ws,
                            hipStream_t st);
 int launch_flow_forward_batch(const float* omega, const float* params, float* z_out, float* sum_log_det,
@@ -236,11 +239,24 @@ int launch_flow_forward_batch(const float* omega, const float* params, float* z_
 int64_t flow_forward_train_workspace(int64_t M, int64_t Mp, int64_t N, int D, int S, int L);
 int launch_flow_forward_train_fwd(const float* omega, const float* params, float* z_out, float* sum_log_det, float* states,
                                   float* folds, float* bn_mean_out, float* bn_alpha_out, int64_t M, int64_t Mp, int64_t N,
-                                  int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st);
+                                  int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st,
+                                  int real_D = 0);
 int launch_flow_forward_train_bwd(const float* omega, const float* params, const float* states, const float* folds,
                                   const float* bn_mean, const float* bn_alpha, const float* g_z, const float* g_sld,
                                   float* g_omega, float* g_params, int64_t M, int64_t Mp, int64_t N, int D, int S, int L,
                                   int U, int64_t pstride, int64_t gpstride, void* ws, hipStream_t st);
+// the embedded layout of a coupling flow of width D inside one of width 2H (flow_pad_train.hip; bn_mean == NULL: no
+// statistics) and the batch-statistics fold for rows in that layout (flow_pad_batch.hip; W = 2H)
+int launch_embed_rows(const float* rows, float* out, int64_t R, int D, hipStream_t st);
+int launch_gather_rows(const float* rows, float* out, int64_t R, int D, hipStream_t st);
+int launch_embed_params(const float* params, const float* bn_mean, const float* bn_alpha, float* params_out,
+                        float* bn_mean_out, float* bn_alpha_out, int64_t Mp, int D, int S, int L, int U, int64_t pstride,
+                        hipStream_t st);
+int launch_gather_params(const float* g, float* g_out, int64_t Mp, int D, int S, int L, int U, int64_t gpstride,
+                         hipStream_t st);
+int launch_pad_finalize_fold(const float* params, int64_t pstride, int64_t affine_off, const double* moments, float eps,
+                             float* mean_out, float* alpha_out, float* fold, float* ldc, int64_t Mp, int W, int real_D,
+                             int has_affine, int first, hipStream_t st);
 // reversible whole-flow training backward (flow_bwd_f16.hip)
 int flow_train_rev_supported(int D, int S, int L, int U);
 int64_t flow_train_rev_workspace(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U);

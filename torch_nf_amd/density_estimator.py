@@ -19,6 +19,12 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          batch_stats_reduce set
   batch_train       forward, fresh       coupling, float32, batch_stats_reduce unset, the chain's    flow_forward_train
                     statistics           shape conditions, M*N >= 32 (one autograd node)
+  batch_chain_      forward, fresh       padded_batch_forward (default off), coupling, inference,    padbatch_ops.flow_padded_
+  padded            statistics           3-d, one parameter row per z row, batch_stats_reduce unset, forward_batch_raw
+                                         fusion AUTO or FLOW, flow_padded_batch_supported (2 <= D <=
+                                         63 but 32: widths the two above never take), M*N > 1
+  batch_train_      forward, fresh       the same with float32 in place of inference, M*N >= 32      padbatch_ops.flow_padded_
+  padded            statistics           (one autograd node)                                         forward_train
   ar_fused          forward (frozen),    AR, plain, const stats, 3-d, ar_flow_supported; forward:    ar_flow_forward_raw,
                     log_prob, inverse    support layer absent or ToInterval                          ar_flow_log_prob_raw
   ar_train          log_prob             AR, fused_ar_training, grad mode on, const stats, float32,  ar_flow_log_prob_train
@@ -41,8 +47,8 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          bijector                                                    bn_apply, bn_batch_forward
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
-a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded` and the per-layer
-chain do not.
+a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, the batch-statistics
+chains (padded or not) and the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
 Sampling: the base density is evaluated first (base_log_density_f64), except that `padded` and the whole-flow `fused`
@@ -53,7 +59,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, ops, padtrain_ops
+from . import _lib, ops, padbatch_ops, padtrain_ops
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -274,6 +280,15 @@ class NormFlow(DensityEstimator):
                 and ops.flow_train_supported(z.size(0), params.size(0), 32, self.D, self.num_stages, self.num_layers,
                                              self.num_units))
 
+    def _padded_batch_ok(self, z, params):
+        """Shapes of the one-call chains with fresh batch statistics at the embedded width 2H (2 <= D <= 63 but 32,
+        num_units <= 16): only with the switch `padded_batch_forward` on, a coupling stack, one parameter row per z row,
+        no sample-sharded statistics, and the fusion setting AUTO or FLOW as for the `padded` family."""
+        return (getattr(self, "padded_batch_forward", False) and self.arch_type == "coupling" and z.dim() == 3
+                and z.size(0) == params.size(0) and self.batch_stats_reduce is None
+                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
+                and padbatch_ops.flow_padded_batch_supported(self.D, self.num_stages, self.num_layers, self.num_units))
+
     def _stats_in_graph(self):
         """Do the cached BatchNorm statistics still carry the graph of the batch-mode forward that produced them
         (per-bijector forward under autograd -- the reference's behaviour, bijectors.py:414-415)?  Then every later
@@ -316,7 +331,7 @@ class NormFlow(DensityEstimator):
         or "inverse") on these tensors.  Pure host logic on the flow's switches and tensor metadata; nothing is
         staged, allocated or launched.  `f32_draw`: the base draw of a "forward" is a float32 tensor, so a
         whole-flow kernel can write log_q itself."""
-        arch, _, stats_graph, f32, _, _ = f = self._facts(z, params)
+        arch, _, stats_graph, f32, _, inference = f = self._facts(z, params)
         sup = self.bijectors[-1].name if self._n_core < len(self.bijectors) else None
         interval = sup == "ToInterval"  # the support layer that a one-kernel family evaluates in its load / store stage
         if arch == "affine" or (op == "inverse" and sup is not None):
@@ -338,6 +353,11 @@ class NormFlow(DensityEstimator):
                 return Route("batch_chain", False, False)
             if f32 and not reduce and self._batch_chain_ok(z, params) and rows >= 32:
                 return Route("batch_train", False, False)
+            if rows > 1 and f32 and self._padded_batch_ok(z, params):  # widths the two above never take
+                if inference:
+                    return Route("batch_chain_padded", False, False)
+                if rows >= 32:
+                    return Route("batch_train_padded", False, False)
             return _BIJECTORS
         if self._padded_ok(z, params, f):
             return Route("padded", False, f32_draw)
@@ -431,6 +451,10 @@ class NormFlow(DensityEstimator):
                 if family == "batch_chain":
                     z, sld, means, alphas = ops.flow_forward_batch_raw(z, p_dev, *shape,
                                                                        reduce_moments=self.batch_stats_reduce)
+                elif family == "batch_chain_padded":  # ... the same two at 2 <= D <= 63 but 32, at the embedded width
+                    z, sld, means, alphas = padbatch_ops.flow_padded_forward_batch_raw(z, p_dev, *shape)
+                elif family == "batch_train_padded":
+                    z, sld, means, alphas = padbatch_ops.flow_padded_forward_train(z, p_dev, *shape)
                 else:
                     z, sld, means, alphas = ops.flow_forward_train(z, p_dev, *shape)
                 for i, b in enumerate(bns):
