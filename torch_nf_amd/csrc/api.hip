@@ -45,8 +45,6 @@ int check_launch(const char* what) {
     return TNF_OK;
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 static int check_mnd(const char* fn, int64_t Mz, int64_t Mp, int64_t N, int D) {
     if (Mz < 1 || Mp < 1 || N < 0) return fail(TNF_EINVAL, "%s: bad batch sizes M_z=%lld M_p=%lld N=%lld", fn, (long long)Mz, (long long)Mp, (long long)N);
     if (Mz != Mp && Mz != 1 && Mp != 1)
@@ -80,8 +78,9 @@ static int check_flow_row(const char* fn, int64_t pstride, int D, int S, int L, 
     return TNF_OK;
 }
 
-static int check_workspace(const char* fn, const void* ws, int64_t ws_bytes, int64_t need) {
+int check_workspace(const char* fn, const void* ws, int64_t ws_bytes, int64_t need, int base_align) {
     if (!ws || ws_bytes < need) return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes, (long long)need);
+    if (!is_aligned(ws, base_align)) return fail(TNF_EWORKSPACE, "%s: the workspace must be %d-byte aligned", fn, base_align);
     return TNF_OK;
 }
 
@@ -95,13 +94,10 @@ static int check_cond_flow(const char* fn, int64_t M, int D, int S, int L, int U
     return TNF_OK;
 }
 
-static int64_t round16(int64_t b) { return (b + 15) & ~(int64_t)15; }
-static inline float* ws_floats(void* ws, int64_t byte_offset) {  // a region of a caller's workspace
-    return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + byte_offset);
-}
-
+// fold (M, 2S, 2, D) | ldc (M) | images (M, 2S, slot) || z (M, N, D) | log-det (M, N): the whole-flow kernels stop at ||
 struct FlowWs {
-    int64_t fold, ldc, images, zbuf, ldbuf, total;
+    float *fold, *ldc, *images, *zbuf, *ldbuf;
+    int64_t fused_bytes, bytes;
 };
 static int64_t flow_image_slot(int D, int L, int U) {
     // narrow shapes: fp32 and split-f16 images share one slot size (the L = 3 fp32 image); flow_ws takes the larger of
@@ -120,16 +116,17 @@ static int64_t flow_prep_slot(int D, int S, int L, int U) {
     }
     return (most + 2 * S - 1) / (2 * S);
 }
-static FlowWs flow_ws(int64_t M, int64_t N, int D, int S, int L, int U) {
+static FlowWs flow_ws(int64_t M, int64_t N, int D, int S, int L, int U, void* ws) {
+    Carver c(ws);
     FlowWs w;
-    w.fold = 0;
-    w.ldc = round16(M * 2 * S * 2 * D * (int64_t)sizeof(float));
-    w.images = w.ldc + round16(M * (int64_t)sizeof(float));
     const int64_t image = flow_image_slot(D, L, U), prep = flow_prep_slot(D, S, L, U);
-    const int64_t slot = image > prep ? image : prep;
-    w.zbuf = w.images + round16(M * 2 * S * slot * (int64_t)sizeof(float));
-    w.ldbuf = w.zbuf + round16(M * N * D * (int64_t)sizeof(float));
-    w.total = w.ldbuf + round16(M * N * (int64_t)sizeof(float));
+    w.fold = c.take<float>(M * 2 * S * 2 * D, 16);
+    w.ldc = c.take<float>(M, 16);
+    w.images = c.take<float>(M * 2 * S * (image > prep ? image : prep), 16);
+    w.fused_bytes = c.bytes(16);
+    w.zbuf = c.take<float>(M * N * D, 16);
+    w.ldbuf = c.take<float>(M * N, 16);
+    w.bytes = c.bytes(16);
     return w;
 }
 
@@ -235,7 +232,7 @@ int tnf_coupling(int32_t dtype, const void* z, const void* params, void* z_out, 
     if (N == 0) return TNF_OK;
     hipStream_t st = as_stream(stream);
     const int64_t Mmax = M_z > M_p ? M_z : M_p;
-    const bool fast = dtype == TNF_F32 && !g_force_generic && aligned16(z) && aligned16(z_out);
+    const bool fast = dtype == TNF_F32 && !g_force_generic && is_aligned(z, 16) && is_aligned(z_out, 16);
     const bool narrow = fast && mfma_supported(D, L, U) && (N >= 16 || Mmax >= 8);
     if (narrow || (fast && wide_supported(D, L, U) && N >= 16)) {
         MfmaLayerArgs a = {};
@@ -277,7 +274,7 @@ int tnf_bn_apply(int32_t dtype, const void* z, const float* mean, const float* a
 
 int64_t tnf_bn_batch_workspace_bytes(int32_t D) {
     if (D < 1) return fail(TNF_EINVAL, "tnf_bn_batch_workspace_bytes: D=%d", D);
-    return round16(2 * (int64_t)D * (int64_t)sizeof(double) + (int64_t)D * (int64_t)sizeof(float));
+    return bn_batch_ws(D, nullptr).bytes;
 }
 
 int tnf_bn_batch_forward_f32(const float* z, float* z_out, float* mean_out, float* alpha_out,
@@ -307,14 +304,14 @@ static int coupling_backward_impl(int32_t dtype, const void* z, const void* para
     if (!z || !params || !g_z_out || !g_log_det || !g_z || !g_params)
         return fail(TNF_EINVAL, "tnf_coupling_backward: NULL pointer");
     if (N == 0) return TNF_OK;
-    if (dtype == TNF_F32 && !g_force_generic && mfma_supported(D, L, U) && N >= 16 && aligned16(z) &&
-        aligned16(g_z_out) && aligned16(g_z))
+    if (dtype == TNF_F32 && !g_force_generic && mfma_supported(D, L, U) && N >= 16 && is_aligned(z, 16) &&
+        is_aligned(g_z_out, 16) && is_aligned(g_z, 16))
         return launch_coupling_backward_mfma((const float*)z, (const float*)params, (const float*)g_z_out,
                                              (const float*)g_log_det, (float*)g_z, (float*)g_params, M, M_p, N,
                                              D, L, U, upper, inverse, pstride, gpstride, as_stream(stream));
     // the wide shapes (num_units up to 64) with one shared parameter row: two-pass MFMA backward (coupling_wide_bwd.hip)
-    if (dtype == TNF_F32 && !g_force_generic && M_p == 1 && ws && wide_bwd_supported(D, L, U) && aligned16(z) &&
-        aligned16(g_z_out) && aligned16(g_z) && aligned16(ws) && ws_bytes >= wide_bwd_workspace(M * N, D, L, U))
+    if (dtype == TNF_F32 && !g_force_generic && M_p == 1 && ws && wide_bwd_supported(D, L, U) && is_aligned(z, 16) &&
+        is_aligned(g_z_out, 16) && is_aligned(g_z, 16) && is_aligned(ws, 16) && ws_bytes >= wide_bwd_workspace(M * N, D, L, U))
         return launch_coupling_backward_wide((const float*)z, (const float*)params, (const float*)g_z_out,
                                              (const float*)g_log_det, (float*)g_z, (float*)g_params, M * N, D, L, U, upper,
                                              inverse, gpstride, ws, as_stream(stream));
@@ -454,7 +451,7 @@ int tnf_ar_flow_supported(int32_t D, int32_t L, int32_t U) { return maf_mfma_sup
 
 int64_t tnf_ar_flow_workspace_bytes(int64_t M_p, int32_t D) {
     if (M_p < 1 || D < 1) return fail(TNF_EINVAL, "tnf_ar_flow_workspace_bytes: M_p=%lld D=%d", (long long)M_p, D);
-    return round16(M_p * (2 * (int64_t)D + 1) * (int64_t)sizeof(float));
+    return ar_flow_ws(M_p, D, false, nullptr).bytes;
 }
 
 static int ar_flow_run(const char* fn, int inverse, const float* z, const float* params, const float* masks,
@@ -473,8 +470,8 @@ static int ar_flow_run(const char* fn, int inverse, const float* z, const float*
     rc = check_workspace(fn, workspace, workspace_bytes, tnf_ar_flow_workspace_bytes(M_p, D));
     if (rc) return rc;
     if (N == 0) return TNF_OK;
-    float* fold = (float*)workspace;
-    float* ldc = fold + M_p * 2 * (int64_t)D;
+    const ArFlowWs w = ar_flow_ws(M_p, D, false, workspace);
+    float *fold = w.fold, *ldc = w.ldc;
     rc = launch_ar_fold(params, pstride, p_maf, bn_mean, bn_alpha, fold, ldc, M_p, D, inverse, as_stream(stream));
     if (rc) return rc;
     MafArgs a = {};
@@ -517,7 +514,7 @@ int tnf_ar_flow_train_supported(int32_t D, int32_t L, int32_t U) {
 
 int64_t tnf_ar_flow_bwd_workspace_bytes(int64_t M_p, int32_t D) {
     if (M_p < 1 || D < 1) return fail(TNF_EINVAL, "tnf_ar_flow_bwd_workspace_bytes: M_p=%lld D=%d", (long long)M_p, D);
-    return round16((M_p * (4 * (int64_t)D + 2) + 1) * (int64_t)sizeof(float));
+    return ar_flow_ws(M_p, D, true, nullptr).bytes;
 }
 
 int tnf_ar_flow_log_prob_bwd_f32(const float* z, const float* params, const float* masks, const float* bn_mean,
@@ -537,13 +534,10 @@ int tnf_ar_flow_log_prob_bwd_f32(const float* z, const float* params, const floa
     rc = check_workspace(fn, workspace, workspace_bytes, tnf_ar_flow_bwd_workspace_bytes(M_p, D));
     if (rc) return rc;
     if (N == 0) return TNF_OK;
-    float* fold = (float*)workspace;
-    float* ldc = fold + M_p * 2 * (int64_t)D;
-    float* g_fold = ldc + M_p;
-    float* glp_sum = g_fold + M_p * 2 * (int64_t)D;
-    rc = launch_ar_fold(params, pstride, p_maf, bn_mean, bn_alpha, fold, ldc, M_p, D, 1, as_stream(stream));
+    const ArFlowWs w = ar_flow_ws(M_p, D, true, workspace);
+    rc = launch_ar_fold(params, pstride, p_maf, bn_mean, bn_alpha, w.fold, w.ldc, M_p, D, 1, as_stream(stream));
     if (rc) return rc;
-    return launch_ar_flow_backward(z, params, masks, fold, interval_consts, g_log_prob, g_params, g_fold, glp_sum, M, M_p,
+    return launch_ar_flow_backward(z, params, masks, w, interval_consts, g_log_prob, g_params, M, M_p,
                                    N, D, L, U, pstride, gpstride, as_stream(stream));
 }
 
@@ -582,8 +576,8 @@ static int maf_backward_impl(int32_t dtype, const void* z, const void* params, c
                                         (const float*)g_log_det, (float*)g_z, (float*)g_params, M, M_p, N, D, L, U,
                                         pstride, gpstride, as_stream(stream));
     // D > 32 (the one-kernel matrix-pipe backward stops there) with one shared parameter row: the two-pass MFMA backward
-    if (dtype == TNF_F32 && !g_force_generic && M_p == 1 && ws && maf_wide_bwd_supported(D, L, U) && aligned16(z) &&
-        aligned16(g_z_out) && aligned16(g_z) && aligned16(ws) && ws_bytes >= maf_wide_bwd_workspace(M * N, D, L, U))
+    if (dtype == TNF_F32 && !g_force_generic && M_p == 1 && ws && maf_wide_bwd_supported(D, L, U) && is_aligned(z, 16) &&
+        is_aligned(g_z_out, 16) && is_aligned(g_z, 16) && is_aligned(ws, 16) && ws_bytes >= maf_wide_bwd_workspace(M * N, D, L, U))
         return launch_maf_backward_wide((const float*)z, (const float*)params, (const float*)masks, (const float*)g_z_out,
                                         (const float*)g_log_det, (float*)g_z, (float*)g_params, M * N, D, L, U, gpstride, ws,
                                         as_stream(stream));
@@ -910,7 +904,7 @@ int tnf_mog_log_prob_backward_f32(const float* z, const float* params, const flo
     const int64_t need = mog_bwd_workspace(M_z > M_p ? M_z : M_p, M_p, N, D, K);
     if (need > 0) {
         if (int rc = check_workspace(fn, workspace, workspace_bytes, need)) return rc;
-        if (!aligned16(workspace)) return fail(TNF_EINVAL, "%s: workspace must be 16-byte aligned", fn);
+        if (!is_aligned(workspace, 16)) return fail(TNF_EINVAL, "%s: workspace must be 16-byte aligned", fn);
     }
     return launch_mog_log_prob_backward(z, params, bounds, g_lp, g_z, g_params, M_z, M_p, N, D, K, ld_params, workspace,
                                         as_stream(stream));
@@ -951,8 +945,8 @@ int64_t tnf_flow_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t S, int
                     (long long)N, D, S, L, U);
     if (!mfma_supported(D, L, U) && !wide_supported(D, L, U))
         return fail(TNF_EUNSUPPORTED, "tnf_flow_workspace_bytes: no fused kernel for D=%d L=%d U=%d", D, L, U);
-    const FlowWs w = flow_ws(M, N, D, S, L, U);
-    return fusion == TNF_FUSE_FLOW ? w.zbuf : w.total;  // the whole-flow kernel needs no z / log-det scratch
+    const FlowWs w = flow_ws(M, N, D, S, L, U, nullptr);
+    return fusion == TNF_FUSE_FLOW ? w.fused_bytes : w.bytes;  // the whole-flow kernel needs no z / log-det scratch
 }
 
 static int flow_common_checks(const char* fn, int64_t M_z, int64_t M_p, int64_t N, int D, int S,
@@ -972,8 +966,8 @@ static int flow_common_checks(const char* fn, int64_t M_z, int64_t M_p, int64_t 
     } else if (fusion == TNF_FUSE_LAYER) *use_fused = 0;
     else return fail(TNF_EINVAL, "%s: fusion %d", fn, fusion);
     const int64_t M = M_z > M_p ? M_z : M_p;
-    const FlowWs w = flow_ws(M, N, D, S, L, U);
-    return check_workspace(fn, ws, ws_bytes, *use_fused ? w.zbuf : w.total);
+    const FlowWs w = flow_ws(M, N, D, S, L, U, nullptr);
+    return check_workspace(fn, ws, ws_bytes, *use_fused ? w.fused_bytes : w.bytes);
 }
 
 // ---- which kernel family a coupling-flow call runs --------------------------------------------------------------------
@@ -1056,7 +1050,7 @@ static int flow_log_prob_impl(const float* z, const float* params, const float* 
     if (rc) return rc;
     if (!z || !params || !bn_mean || !bn_alpha) return fail(TNF_EINVAL, "tnf_flow_log_prob_f32: NULL pointer");
     if (!log_prob && !z0 && !sum_log_det) return fail(TNF_EINVAL, "tnf_flow_log_prob_f32: no output requested");
-    if (!aligned16(z) || (z0 && !aligned16(z0)))
+    if (!is_aligned(z, 16) || (z0 && !is_aligned(z0, 16)))
         return fail(TNF_EINVAL, "tnf_flow_log_prob_f32: z / z0 must be 16-byte aligned");
     if (z0 == z) return fail(TNF_EINVAL, "tnf_flow_log_prob_f32: z0 must not alias z");
     if (N == 0) return TNF_OK;
@@ -1064,13 +1058,11 @@ static int flow_log_prob_impl(const float* z, const float* params, const float* 
                                             interval_consts != nullptr, false, fusion, flow_options());
     hipStream_t st = as_stream(stream);
     const int64_t M = M_z > M_p ? M_z : M_p;
-    const FlowWs w = flow_ws(M, N, D, S, L, U);
-    float* fold = ws_floats(workspace, w.fold);
-    float* ldc = ws_floats(workspace, w.ldc);
-    float* images = ws_floats(workspace, w.images);
+    const FlowWs w = flow_ws(M, N, D, S, L, U, workspace);
+    float *fold = w.fold, *ldc = w.ldc, *images = w.images;
     // z / log-det scratch of the chains (the whole-flow workspace has none)
-    float* zbuf = use_fused ? nullptr : (z0 ? z0 : ws_floats(workspace, w.zbuf));
-    float* ldbuf = use_fused ? nullptr : (sum_log_det ? sum_log_det : ws_floats(workspace, w.ldbuf));
+    float* zbuf = use_fused ? nullptr : (z0 ? z0 : w.zbuf);
+    float* ldbuf = use_fused ? nullptr : (sum_log_det ? sum_log_det : w.ldbuf);
     switch (k.family) {
         case FLOW_REFUSED: return k.rc;
         case FLOW_BF16_RANGE:  // the bf16 experiment runs on the layer-range kernel
@@ -1158,18 +1150,26 @@ int tnf_flow_log_prob_diag_f32(const float* z, const float* params, const float*
 
 // ---- training pair: log_prob with saved per-layer inputs, and its backward ----
 struct TrainWs {
-    int64_t fold, ldc, images, gfold, ldbuf, gbuf, total;
+    float *fold, *ldc, *images, *gfold, *glp_sum, *ldbuf, *gbuf[2];
+    unsigned* gmax;
+    int64_t zeroed_bytes, bytes;  // zeroed as one block: gfold .. gmax
 };
-static TrainWs train_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L) {
+static TrainWs train_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, void* ws) {
+    Carver c(ws);
     TrainWs w;
-    w.fold = 0;
-    w.ldc = round16(Mp * 2 * S * 2 * D * (int64_t)sizeof(float));
-    w.images = w.ldc + round16(Mp * (int64_t)sizeof(float));
-    w.gfold = w.images + round16(Mp * 2 * S * mfma_image_floats(D, L) * (int64_t)sizeof(float));
-    // g_fold (Mp, 2S, 2, D) followed by the per-row sums of g_log_prob (Mp): zeroed together
-    w.ldbuf = w.gfold + round16((Mp * 2 * S * 2 * D + Mp + 1) * (int64_t)sizeof(float));  // + max |g_log_prob|
-    w.gbuf = w.ldbuf + round16(M * N * (int64_t)sizeof(float));
-    w.total = w.gbuf + 2 * round16(M * N * D * (int64_t)sizeof(float));
+    w.fold = c.take<float>(Mp * 2 * S * 2 * D, 16);
+    w.ldc = c.take<float>(Mp, 16);
+    w.images = c.take<float>(Mp * 2 * S * mfma_image_floats(D, L), 16);
+    // g_fold (Mp, 2S, 2, D) followed by the per-row sums of g_log_prob (Mp) and max |g_log_prob|
+    const int64_t zeroed_from = c.bytes(16);
+    w.gfold = c.take<float>(Mp * 2 * S * 2 * D, 16);
+    w.glp_sum = c.take<float>(Mp, 4);
+    w.gmax = c.take<unsigned>(1, 4);
+    w.zeroed_bytes = c.bytes() - zeroed_from;
+    w.ldbuf = c.take<float>(M * N, 16);
+    w.gbuf[0] = c.take<float>(M * N * D, 16);
+    w.gbuf[1] = c.take<float>(M * N * D, 16);
+    w.bytes = c.bytes(16);
     return w;
 }
 
@@ -1177,7 +1177,7 @@ int64_t tnf_flow_train_workspace_bytes(int64_t M, int64_t M_p, int64_t N, int32_
     if (int rc = check_batch_stages("tnf_flow_train_workspace_bytes", M, M_p, N, S)) return rc;
     if (!mfma_supported(D, L, U))
         return fail(TNF_EUNSUPPORTED, "tnf_flow_train_workspace_bytes: no training kernels for D=%d L=%d U=%d", D, L, U);
-    return train_ws(M, M_p, N, D, S, L).total;
+    return train_ws(M, M_p, N, D, S, L, nullptr).bytes;
 }
 
 // the chains that exist for the narrow shapes only (training pair, batch-statistics forward and its training pair): batch,
@@ -1197,18 +1197,15 @@ int tnf_flow_log_prob_fwd_f32(const float* z, const float* params, const float* 
                               int64_t workspace_bytes, void* stream) {
     const char* fn = "tnf_flow_log_prob_fwd_f32";
     int rc = narrow_chain_checks(fn, M, M_p, N, D, S, L, U, false, pstride);
-    if (!rc) rc = check_workspace(fn, workspace, workspace_bytes, train_ws(M, M_p, N, D, S, L).total);
+    if (!rc) rc = check_workspace(fn, workspace, workspace_bytes, train_ws(M, M_p, N, D, S, L, nullptr).bytes);
     if (rc) return rc;
     if (!z || !params || !bn_mean || !bn_alpha || !log_prob || !states)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (!aligned16(z) || !aligned16(states)) return fail(TNF_EINVAL, "%s: z / states must be 16-byte aligned", fn);
+    if (!is_aligned(z, 16) || !is_aligned(states, 16)) return fail(TNF_EINVAL, "%s: z / states must be 16-byte aligned", fn);
     if (N == 0) return TNF_OK;
     hipStream_t st = as_stream(stream);
-    const TrainWs w = train_ws(M, M_p, N, D, S, L);
-    float* fold = ws_floats(workspace, w.fold);
-    float* ldc = ws_floats(workspace, w.ldc);
-    float* images = ws_floats(workspace, w.images);
-    float* ldbuf = ws_floats(workspace, w.ldbuf);
+    const TrainWs w = train_ws(M, M_p, N, D, S, L, workspace);
+    float *fold = w.fold, *ldc = w.ldc, *images = w.images, *ldbuf = w.ldbuf;
     rc = launch_flow_prep(params, bn_mean, bn_alpha, fold, ldc, images, M_p, D, S, L, U, pstride, 1, st);
     if (rc) return rc;
     const FlowLayout fl = flow_layout(D, S, L, U);
@@ -1246,24 +1243,19 @@ int tnf_flow_log_prob_bwd_f32(const float* z, const float* states, const float* 
                               void* stream) {
     const char* fn = "tnf_flow_log_prob_bwd_f32";
     int rc = narrow_chain_checks(fn, M, M_p, N, D, S, L, U, false, pstride);
-    if (!rc) rc = check_workspace(fn, workspace, workspace_bytes, train_ws(M, M_p, N, D, S, L).total);
+    if (!rc) rc = check_workspace(fn, workspace, workspace_bytes, train_ws(M, M_p, N, D, S, L, nullptr).bytes);
     if (rc) return rc;
     if (!z || !states || !params || !bn_mean || !bn_alpha || !g_log_prob || !g_z || !g_params)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
     if (gpstride < flow_layout(D, S, L, U).total) return fail(TNF_EINVAL, "%s: g_params row too short", fn);
     if (N == 0) return TNF_OK;
     hipStream_t st = as_stream(stream);
-    const TrainWs w = train_ws(M, M_p, N, D, S, L);
-    float* fold = ws_floats(workspace, w.fold);
-    float* ldc = ws_floats(workspace, w.ldc);
-    float* images = ws_floats(workspace, w.images);
-    float* gfold = ws_floats(workspace, w.gfold);
-    float* gbuf[2] = {ws_floats(workspace, w.gbuf), ws_floats(workspace, w.gbuf + round16(M * N * D * (int64_t)sizeof(float)))};
+    const TrainWs w = train_ws(M, M_p, N, D, S, L, workspace);
+    float *fold = w.fold, *ldc = w.ldc, *images = w.images, *gfold = w.gfold, *glp_sum = w.glp_sum, *const *gbuf = w.gbuf;
+    unsigned* gmaxw = w.gmax;
     rc = launch_flow_prep(params, bn_mean, bn_alpha, fold, ldc, images, M_p, D, S, L, U, pstride, 1, st);
     if (rc) return rc;
-    float* glp_sum = gfold + M_p * 2 * S * 2 * D;
-    unsigned* gmaxw = reinterpret_cast<unsigned*>(glp_sum + M_p);
-    if (hipMemsetAsync(gfold, 0, (size_t)(M_p * 2 * S * 2 * D + M_p + 1) * sizeof(float), st) != hipSuccess)
+    if (hipMemsetAsync(gfold, 0, (size_t)w.zeroed_bytes, st) != hipSuccess)
         return fail(TNF_ELAUNCH, "%s: memset failed", fn);
     rc = launch_gmax(g_log_prob, M * N, gmaxw, st);
     if (rc) return rc;
@@ -1326,7 +1318,7 @@ int tnf_flow_log_prob_fwd_rev_f32(const float* z, const float* params, const flo
     if (N == 0) return TNF_OK;
     if (!z || !params || !bn_mean || !bn_alpha || !log_prob || !z0)
         return fail(TNF_EINVAL, "tnf_flow_log_prob_fwd_rev_f32: NULL pointer");
-    if (!aligned16(z) || !aligned16(z0)) return fail(TNF_EINVAL, "tnf_flow_log_prob_fwd_rev_f32: z / z0 must be 16-byte aligned");
+    if (!is_aligned(z, 16) || !is_aligned(z0, 16)) return fail(TNF_EINVAL, "tnf_flow_log_prob_fwd_rev_f32: z / z0 must be 16-byte aligned");
     const FlowChoice k = select_flow_kernel("tnf_flow_log_prob_fwd_rev_f32", FLOW_REV_FORWARD, true, D, S, L, U, false, false,
                                             TNF_FUSE_FLOW, flow_options());
     hipStream_t st = as_stream(stream);
@@ -1357,7 +1349,7 @@ int tnf_flow_log_prob_bwd_rev_f32(const float* z0, const float* params, const fl
     if (N == 0) return TNF_OK;
     if (!z0 || !params || !bn_mean || !bn_alpha || !g_log_prob || !g_params)
         return fail(TNF_EINVAL, "tnf_flow_log_prob_bwd_rev_f32: NULL pointer");
-    if (!aligned16(z0) || (g_z && !aligned16(g_z)))
+    if (!is_aligned(z0, 16) || (g_z && !is_aligned(g_z, 16)))
         return fail(TNF_EINVAL, "tnf_flow_log_prob_bwd_rev_f32: z0 / g_z must be 16-byte aligned");
     if (gpstride < flow_layout(D, S, L, U).total)
         return fail(TNF_EINVAL, "tnf_flow_log_prob_bwd_rev_f32: g_params row too short");
@@ -1383,7 +1375,7 @@ int tnf_flow_forward_batch_f32(const float* omega, const float* params, float* z
     if (rc) return rc;
     if (!omega || !params || !z_out || !sum_log_det || !bn_mean_out || !bn_alpha_out || !workspace)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (!aligned16(omega) || !aligned16(z_out)) return fail(TNF_EINVAL, "%s: omega / z_out must be 16-byte aligned", fn);
+    if (!is_aligned(omega, 16) || !is_aligned(z_out, 16)) return fail(TNF_EINVAL, "%s: omega / z_out must be 16-byte aligned", fn);
     if (z_out == omega) return fail(TNF_EINVAL, "%s: z_out must not alias omega", fn);
     rc = check_workspace(fn, workspace, workspace_bytes, flow_forward_batch_workspace(M_p, D, S, L));
     if (rc) return rc;
@@ -1421,7 +1413,7 @@ int tnf_flow_forward_batch_layer_f32(int32_t layer, const float* z_in, const flo
     if (rc) return rc;
     if (layer < 0 || layer >= 2 * S) return fail(TNF_EINVAL, "%s: layer %d of %d", fn, layer, 2 * S);
     if (!params || !moments || (N > 0 && (!z_in || !z_out || !sum_log_det))) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (!aligned16(z_in) || !aligned16(z_out) || (reinterpret_cast<uintptr_t>(moments) & 7))
+    if (!is_aligned(z_in, 16) || !is_aligned(z_out, 16) || !is_aligned(moments, 8))
         return fail(TNF_EINVAL, "%s: z_in / z_out must be 16-byte and moments 8-byte aligned", fn);
     if (layer == 0 && z_in == z_out) return fail(TNF_EINVAL, "%s: z_out must not alias the base draw", fn);
     return flow_forward_batch_layer(layer, z_in, params, z_out, sum_log_det, moments, M, M_p, N, D, S, L, U, pstride,
@@ -1448,7 +1440,7 @@ int tnf_flow_forward_batch_end_f32(float* z_out, float* sum_log_det, int64_t M, 
     if (!workspace || workspace_bytes < flow_forward_batch_workspace(M_p, D, S, L))
         return fail(TNF_EWORKSPACE, "%s: workspace too small", fn);
     if (N > 0 && (!z_out || !sum_log_det)) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    return flow_forward_batch_end(z_out, sum_log_det, M, M_p, N, D, workspace, as_stream(stream));
+    return flow_forward_batch_end(z_out, sum_log_det, M, M_p, N, D, S, L, workspace, as_stream(stream));
 }
 
 // ... and the same stack under autograd (sampling-based objectives): forward keeps every coupling layer's output
@@ -1469,7 +1461,7 @@ int tnf_flow_forward_train_fwd_f32(const float* omega, const float* params, floa
     if (rc) return rc;
     if (!omega || !params || !z_out || !sum_log_det || !states || !folds || !bn_mean_out || !bn_alpha_out)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (!aligned16(omega) || !aligned16(z_out) || !aligned16(states))
+    if (!is_aligned(omega, 16) || !is_aligned(z_out, 16) || !is_aligned(states, 16))
         return fail(TNF_EINVAL, "%s: omega / z_out / states must be 16-byte aligned", fn);
     return launch_flow_forward_train_fwd(omega, params, z_out, sum_log_det, states, folds, bn_mean_out, bn_alpha_out, M, M_p,
                                          N, D, S, L, U, pstride, eps, workspace, as_stream(stream));
@@ -1487,8 +1479,8 @@ int tnf_flow_forward_train_bwd_f32(const float* omega, const float* params, cons
     if (!omega || !params || !states || !folds || !bn_mean || !bn_alpha || !g_z || !g_sum_log_det || !g_params)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
     if (gpstride < flow_layout(D, S, L, U).total) return fail(TNF_EINVAL, "%s: g_params row too short", fn);
-    if (!aligned16(omega) || !aligned16(states) || !aligned16(g_z) || (g_omega && !aligned16(g_omega)) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 255))
+    if (!is_aligned(omega, 16) || !is_aligned(states, 16) || !is_aligned(g_z, 16) || (g_omega && !is_aligned(g_omega, 16)) ||
+        !is_aligned(workspace, 256))
         return fail(TNF_EINVAL, "%s: omega / states / g_z / g_omega must be 16-byte and the workspace 256-byte aligned", fn);
     return launch_flow_forward_train_bwd(omega, params, states, folds, bn_mean, bn_alpha, g_z, g_sum_log_det, g_omega,
                                          g_params, M, M_p, N, D, S, L, U, pstride, gpstride, workspace, as_stream(stream));
@@ -1506,7 +1498,7 @@ static int flow_forward_impl(const float* omega, const float* params, const floa
     if (rc) return rc;
     if (!omega || !params || !bn_mean || !bn_alpha || !z_out || !sum_log_det)
         return fail(TNF_EINVAL, "tnf_flow_forward_f32: NULL pointer");
-    if (!aligned16(omega) || !aligned16(z_out))
+    if (!is_aligned(omega, 16) || !is_aligned(z_out, 16))
         return fail(TNF_EINVAL, "tnf_flow_forward_f32: omega / z_out must be 16-byte aligned");
     if (z_out == omega) return fail(TNF_EINVAL, "tnf_flow_forward_f32: z_out must not alias omega");
     if (N == 0) return TNF_OK;
@@ -1514,10 +1506,8 @@ static int flow_forward_impl(const float* omega, const float* params, const floa
                                             interval_consts != nullptr, log_q != nullptr, fusion, flow_options());
     hipStream_t st = as_stream(stream);
     const int64_t M = M_z > M_p ? M_z : M_p;
-    const FlowWs w = flow_ws(M, N, D, S, L, U);
-    float* fold = ws_floats(workspace, w.fold);
-    float* ldc = ws_floats(workspace, w.ldc);
-    float* images = ws_floats(workspace, w.images);
+    const FlowWs w = flow_ws(M, N, D, S, L, U, workspace);
+    float *fold = w.fold, *ldc = w.ldc, *images = w.images;
     switch (k.family) {
         case FLOW_REFUSED: return k.rc;
         case FLOW_FUSED2:  // f16_tile2.h, FWD
@@ -1598,7 +1588,7 @@ int64_t tnf_flow_padded_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t
                     (long long)N, D, S, L, U);
     if (!flow_padded_supported(D, S, L, U))
         return fail(TNF_EUNSUPPORTED, "tnf_flow_padded_workspace_bytes: no padded kernel for D=%d S=%d L=%d U=%d", D, S, L, U);
-    return round16(M * 16);  // one reserved 16-byte slot per context; the kernel's scratch is its LDS
+    return round_up(M * 16, 16);  // one reserved 16-byte slot per context; the kernel's scratch is its LDS
 }
 
 static int flow_padded_checks(const char* fn, const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
@@ -1615,8 +1605,6 @@ static int flow_padded_checks(const char* fn, const float* z, const float* param
     return check_workspace(fn, ws, ws_bytes, tnf_flow_padded_workspace_bytes(M_z > M_p ? M_z : M_p, N, D, S, L, U));
 }
 
-static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 int tnf_flow_padded_log_prob_f32(const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
                                  float* log_prob, float* z0, float* sum_log_det, int64_t M_z, int64_t M_p, int64_t N,
                                  int32_t D, int32_t S, int32_t L, int32_t U, int64_t pstride, void* workspace,
@@ -1625,7 +1613,7 @@ int tnf_flow_padded_log_prob_f32(const float* z, const float* params, const floa
     int rc = flow_padded_checks(fn, z, params, bn_mean, bn_alpha, M_z, M_p, N, D, S, L, U, pstride, workspace, workspace_bytes);
     if (rc) return rc;
     if (!log_prob && !z0 && !sum_log_det) return fail(TNF_EINVAL, "%s: no output requested", fn);
-    if (!aligned4(z) || (z0 && !aligned4(z0)) || (log_prob && !aligned4(log_prob)) || (sum_log_det && !aligned4(sum_log_det)))
+    if (!is_aligned(z, 4) || (z0 && !is_aligned(z0, 4)) || (log_prob && !is_aligned(log_prob, 4)) || (sum_log_det && !is_aligned(sum_log_det, 4)))
         return fail(TNF_EINVAL, "%s: z and the outputs must be 4-byte aligned", fn);
     if (z0 == z) return fail(TNF_EINVAL, "%s: z0 must not alias z", fn);
     if (N == 0) return TNF_OK;
@@ -1642,7 +1630,7 @@ int tnf_flow_padded_forward_f32(const float* omega, const float* params, const f
                                 workspace_bytes);
     if (rc) return rc;
     if (!z_out || !sum_log_det) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (!aligned4(omega) || !aligned4(z_out) || !aligned4(sum_log_det) || (log_q && (reinterpret_cast<uintptr_t>(log_q) & 7u)))
+    if (!is_aligned(omega, 4) || !is_aligned(z_out, 4) || !is_aligned(sum_log_det, 4) || (log_q && !is_aligned(log_q, 8)))
         return fail(TNF_EINVAL, "%s: omega and the outputs must be 4-byte aligned (log_q 8-byte)", fn);
     if (z_out == omega) return fail(TNF_EINVAL, "%s: z_out must not alias omega", fn);
     if (N == 0) return TNF_OK;

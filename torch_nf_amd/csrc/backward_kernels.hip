@@ -519,7 +519,7 @@ int launch_bn_batch_backward_apply(const float* zn, const float* g, const float*
 }
 int launch_bn_batch_backward(const float* zn, const float* g, const float* g_ld, const float* alpha, float* g_z,
                              int64_t rows, int D, void* ws, hipStream_t st) {
-    double* sums = reinterpret_cast<double*>(ws);
+    double* sums = bn_batch_ws(D, ws).sums;
     const int rc = launch_bn_batch_backward_sums(zn, g, sums, rows, D, st);
     if (rc) return rc;
     return launch_bn_batch_backward_apply(zn, g, g_ld, alpha, sums, nullptr, g_z, rows, D, st);

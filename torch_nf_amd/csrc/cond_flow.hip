@@ -469,11 +469,7 @@ bool cond_flow_supported(int D, int S, int L, int U, int H) {
     return (D == 32 || D == 64) && S >= 1 && L >= 1 && L <= 5 && U >= 1 && U <= 16 && (H == 32 || H == 64 || H == 128);
 }
 
-static int64_t cond_image_bytes(const CondCfg& c) { return c.T * (int64_t)(c.H / 32 * 128 + 4) * 16; }
-
-int64_t cond_flow_workspace(int D, int S, int L, int U, int H) {
-    return 256 + cond_image_bytes(cond_cfg(D, S, L, U, H));
-}
+int64_t cond_flow_workspace(int D, int S, int L, int U, int H) { return cond_ws(cond_cfg(D, S, L, U, H), false, nullptr).bytes; }
 
 template <int DT, int KS, int BT, int NW, bool SAVE, bool FWD = false>
 static int launch_cond_variant(const CondArgs& a, hipStream_t st) {
@@ -510,14 +506,14 @@ static int launch_cond_dk(const CondArgs& a, hipStream_t st) {
     return launch_cond_variant<DT, KS, 1, 4, false>(a, st);
 }
 
-// absmax -> power-of-two scale (ws[0]: max bits, ws[1]: 1/scale) and the operand image in forward or
+// absmax -> power-of-two scale (max bits, 1/scale in the workspace's head) and the operand image in forward or
 // backward tile order
-int launch_cond_image(const float* W, const float* b, int64_t ldw, const CondCfg& cfg, void* ws, void* image,
-                      int backward_order, hipStream_t st) {
-    unsigned* maxbits = reinterpret_cast<unsigned*>(ws);
-    float* inv_scale = reinterpret_cast<float*>(ws) + 1;
-    u4* img = reinterpret_cast<u4*>(image);
-    if (hipMemsetAsync(maxbits, 0, 8, st) != hipSuccess) return fail(TNF_ELAUNCH, "cond_flow: memset failed");
+int launch_cond_image(const float* W, const float* b, int64_t ldw, const CondCfg& cfg, const CondWs& w, int backward_order,
+                      hipStream_t st) {
+    unsigned* maxbits = w.maxbits;
+    float* inv_scale = w.inv_scale;
+    u4* img = w.pimg;
+    if (hipMemsetAsync(maxbits, 0, (size_t)w.scale_bytes, st) != hipSuccess) return fail(TNF_ELAUNCH, "cond_flow: memset failed");
     hipLaunchKernelGGL(cond_absmax_kernel, dim3(256), dim3(256), 0, st, W, b, cfg.fl.total, cfg.H, ldw, maxbits);
     const unsigned ib = (unsigned)((cfg.T + 3) / 4);
     if (cfg.H == 32)
@@ -529,20 +525,19 @@ int launch_cond_image(const float* W, const float* b, int64_t ldw, const CondCfg
     return check_launch("cond_flow_prep");
 }
 
-int launch_cond_flow_log_prob(const float* z, const float* h, const float* W, const float* b, const float* bn_mean,
-                              const float* bn_alpha, float* log_prob, float* z0, float* sum_log_det, float* acts,
-                              int64_t M, int D, int S, int L, int U, int H, int64_t ldh, int64_t ldw, void* ws,
-                              hipStream_t st) {
+// both directions: the workspace carved (cond_ws), the operand image built in tile order `order`, then the kernel
+static int launch_cond(int order, const float* z, const float* h, const float* W, const float* b, const float* bn_mean,
+                       const float* bn_alpha, float* log_prob, float* z0, float* sum_log_det, float* acts, int64_t M, int D,
+                       int S, int L, int U, int H, int64_t ldh, int64_t ldw, void* ws, hipStream_t st) {
     const CondCfg cfg = cond_cfg(D, S, L, U, H);
-    float* inv_scale = reinterpret_cast<float*>(ws) + 1;
-    u4* image = reinterpret_cast<u4*>(reinterpret_cast<char*>(ws) + 256);
-    int rc = launch_cond_image(W, b, ldw, cfg, ws, image, 0, st);
+    const CondWs w = cond_ws(cfg, false, ws);
+    int rc = launch_cond_image(W, b, ldw, cfg, w, order, st);
     if (rc) return rc;
+    const CondActs saved = cond_acts(M, D, S, L, acts);  // acts == NULL: nothing is saved
     CondArgs a;
-    a.z = z; a.h = h; a.image = image; a.inv_scale = inv_scale; a.bn_mean = bn_mean; a.bn_alpha = bn_alpha;
+    a.z = z; a.h = h; a.image = w.pimg; a.inv_scale = w.inv_scale; a.bn_mean = bn_mean; a.bn_alpha = bn_alpha;
     a.log_prob = log_prob; a.z0 = z0; a.sum_log_det = sum_log_det;
-    a.acts_aff = acts;
-    a.acts_c = acts ? acts + (int64_t)S * M * D : nullptr;
+    a.acts_aff = saved.aff; a.acts_c = saved.c;
     a.M = M; a.ldh = ldh; a.T = cfg.T; a.S = S; a.L = L; a.U = U;
     if (D == 64) {
         if (H == 32) return launch_cond_dk<4, 1>(a, st);
@@ -554,30 +549,20 @@ int launch_cond_flow_log_prob(const float* z, const float* h, const float* W, co
     return launch_cond_dk<2, 4>(a, st);
 }
 
+int launch_cond_flow_log_prob(const float* z, const float* h, const float* W, const float* b, const float* bn_mean,
+                              const float* bn_alpha, float* log_prob, float* z0, float* sum_log_det, float* acts,
+                              int64_t M, int D, int S, int L, int U, int H, int64_t ldh, int64_t ldw, void* ws,
+                              hipStream_t st) {
+    return launch_cond(0, z, h, W, b, bn_mean, bn_alpha, log_prob, z0, sum_log_det, acts, M, D, S, L, U, H, ldh, ldw, ws, st);
+}
+
 // ConditionalDensityEstimator.__call__(x, N = 1) with frozen statistics: omega (M, D) base draws -> z_out (M, D),
 // sum_log_det (M); the same kernel with the sampling program.
 int launch_cond_flow_forward(const float* omega, const float* h, const float* W, const float* b, const float* bn_mean,
                              const float* bn_alpha, float* z_out, float* sum_log_det, int64_t M, int D, int S, int L, int U,
                              int H, int64_t ldh, int64_t ldw, void* ws, hipStream_t st) {
-    const CondCfg cfg = cond_cfg(D, S, L, U, H);
-    float* inv_scale = reinterpret_cast<float*>(ws) + 1;
-    u4* image = reinterpret_cast<u4*>(reinterpret_cast<char*>(ws) + 256);
-    int rc = launch_cond_image(W, b, ldw, cfg, ws, image, 2, st);
-    if (rc) return rc;
-    CondArgs a;
-    a.z = omega; a.h = h; a.image = image; a.inv_scale = inv_scale; a.bn_mean = bn_mean; a.bn_alpha = bn_alpha;
-    a.log_prob = nullptr; a.z0 = z_out; a.sum_log_det = sum_log_det;
-    a.acts_aff = nullptr;
-    a.acts_c = nullptr;
-    a.M = M; a.ldh = ldh; a.T = cfg.T; a.S = S; a.L = L; a.U = U;
-    if (D == 64) {
-        if (H == 32) return launch_cond_dk<4, 1>(a, st);
-        if (H == 64) return launch_cond_dk<4, 2>(a, st);
-        return launch_cond_dk<4, 4>(a, st);
-    }
-    if (H == 32) return launch_cond_dk<2, 1>(a, st);
-    if (H == 64) return launch_cond_dk<2, 2>(a, st);
-    return launch_cond_dk<2, 4>(a, st);
+    return launch_cond(2, omega, h, W, b, bn_mean, bn_alpha, nullptr, z_out, sum_log_det, nullptr, M, D, S, L, U, H, ldh, ldw,
+                       ws, st);
 }
 
 }  // namespace tnf

@@ -1040,17 +1040,10 @@ cond_gw_kernel(GwArgs a) {
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-int64_t cond_acts_floats(int64_t M, int D, int S, int L) { return (int64_t)S * M * D + 2 * (int64_t)S * M * (3 * (D / 2) + 32 * L); }
-// deltas of every layer + the pre-split h image of the g_W kernel (H floats per context, 32-context groups)
-int64_t cond_deltas_floats(int64_t M, int D, int S, int L, int H) {
-    return 2 * (int64_t)S * M * D + 2 * (int64_t)S * M * (D + 32 * L) + ((M + 31) / 32) * 32 * (int64_t)H;
-}
+int64_t cond_acts_floats(int64_t M, int D, int S, int L) { return cond_acts(M, D, S, L, nullptr).floats; }
+int64_t cond_deltas_floats(int64_t M, int D, int S, int L, int H) { return cond_deltas(M, D, S, L, H, nullptr).floats; }
 
-int64_t cond_flow_bwd_workspace(int D, int S, int L, int U, int H) {
-    const CondCfg c = cond_cfg(D, S, L, U, H);
-    const int KS = H / 32;
-    return 256 + c.T * (int64_t)(KS * 128 + 4) * 16 + (c.T / 2) * (int64_t)(KS * 256) * 16;
-}
+int64_t cond_flow_bwd_workspace(int D, int S, int L, int U, int H) { return cond_ws(cond_cfg(D, S, L, U, H), true, nullptr).bytes; }
 
 template <int DT, int KS, int BT, int NW>
 static int launch_gh(const CondBwdArgs& a, hipStream_t st) {
@@ -1121,18 +1114,17 @@ int launch_cond_flow_backward(const float* g_lp, const float* h, const float* W,
                               int64_t ldw, int64_t ldgh, int64_t ldgw, void* ws, hipStream_t st) {
     const CondCfg cfg = cond_cfg(D, S, L, U, H);
     const int KS = H / 32;
-    char* base = reinterpret_cast<char*>(ws);
-    u4* pimg = reinterpret_cast<u4*>(base + 256);
-    u4* timg = pimg + cfg.T * (int64_t)(KS * 128 + 4);
-    int rc = launch_cond_image(W, b, ldw, cfg, ws, pimg, 1, st);
+    const CondWs w = cond_ws(cfg, true, ws);
+    u4 *pimg = w.pimg, *timg = w.timg;
+    int rc = launch_cond_image(W, b, ldw, cfg, w, 1, st);
     if (rc) return rc;
-    const unsigned* maxbits = reinterpret_cast<const unsigned*>(ws);
+    const unsigned* maxbits = w.maxbits;
     const unsigned tb = (unsigned)((cfg.T / 2 + 3) / 4);
     if (KS == 1) hipLaunchKernelGGL(cond_timage_kernel<1>, dim3(tb), dim3(256), 0, st, W, ldw, cfg, maxbits, timg);
     else if (KS == 2) hipLaunchKernelGGL(cond_timage_kernel<2>, dim3(tb), dim3(256), 0, st, W, ldw, cfg, maxbits, timg);
     else hipLaunchKernelGGL(cond_timage_kernel<4>, dim3(tb), dim3(256), 0, st, W, ldw, cfg, maxbits, timg);
-    unsigned* gmax = reinterpret_cast<unsigned*>(ws) + 2;
-    if (hipMemsetAsync(gmax, 0, 4, st) != hipSuccess) return fail(TNF_ELAUNCH, "cond_flow_bwd: memset failed");
+    unsigned* gmax = w.gmax;
+    if (hipMemsetAsync(gmax, 0, sizeof(unsigned), st) != hipSuccess) return fail(TNF_ELAUNCH, "cond_flow_bwd: memset failed");
     hipLaunchKernelGGL(cond_gmax_kernel, dim3(64), dim3(256), 0, st, g_lp, M, gmax);
     rc = check_launch("cond_flow_bwd_prep");
     if (rc) return rc;
@@ -1140,15 +1132,17 @@ int launch_cond_flow_backward(const float* g_lp, const float* h, const float* W,
         hipMemsetAsync(g_b, 0, (size_t)cfg.fl.total * sizeof(float), st) != hipSuccess)
         return fail(TNF_ELAUNCH, "cond_flow_bwd: memset failed");
     CondBwdArgs a;
-    a.g_lp = g_lp; a.gmaxbits = gmax; a.h = h; a.pimg = pimg; a.timg = timg; a.inv_scale = reinterpret_cast<const float*>(ws) + 1;
+    a.g_lp = g_lp; a.gmaxbits = gmax; a.h = h; a.pimg = pimg; a.timg = timg; a.inv_scale = w.inv_scale;
     a.bn_mean = bn_mean; a.bn_alpha = bn_alpha;
-    a.acts_aff = acts; a.acts_c = acts + (int64_t)S * M * D;
-    a.d_aff = deltas; a.d_c = deltas + 2 * (int64_t)S * M * D;
+    const CondActs saved = cond_acts(M, D, S, L, const_cast<float*>(acts));
+    const CondDeltas dl = cond_deltas(M, D, S, L, H, deltas);
+    a.acts_aff = saved.aff; a.acts_c = saved.c;
+    a.d_aff = dl.aff; a.d_c = dl.c;
     a.g_h = g_h; a.g_z = g_z; a.M = M; a.ldh = ldh; a.ldgh = ldgh; a.T = cfg.T; a.S = S; a.L = L; a.U = U;
     GwArgs g;
     g.h = h; g.acts_c = a.acts_c; g.d_c = a.d_c; g.d_aff = a.d_aff; g.g_W = g_W; g.g_b = g_b;
     g.M = M; g.ldh = ldh; g.ldgw = ldgw; g.cfg = cfg; g.gmaxbits = gmax;
-    g.himg = reinterpret_cast<const u4*>(a.d_c + 2 * (int64_t)S * M * (D + 32 * L));  // 16-byte aligned: all terms are
+    g.himg = reinterpret_cast<const u4*>(dl.himg);
     if (D == 64) {
         if (KS == 1) return launch_bwd_dk<4, 1>(a, g, st);
         if (KS == 2) return launch_bwd_dk<4, 2>(a, g, st);

@@ -265,8 +265,54 @@ template <int KS> constexpr int kCondG = 8 / KS;  // tiles per LDS chunk (~16.5 
 // ring depth of the forward stream: 3 slots when the 160 KB of LDS allow it next to the waves' state
 template <int KS, int BT, int NW> constexpr int kCondNS = (NW * BT <= 16) ? 3 : 2;
 
-int launch_cond_image(const float* W, const float* b, int64_t ldw, const CondCfg& cfg, void* ws, void* image,
-                      int backward_order, hipStream_t st);
+// ---- workspace and caller-owned buffers of the conditional-flow entries, each described once (workspace.h) ----
+// head [max |W, b| bits | 1 / scale | max |g_log_prob| bits], 256 bytes | operand image | transposed image (backward)
+struct CondWs {
+    unsigned *maxbits, *gmax;
+    float* inv_scale;
+    u4 *pimg, *timg;
+    int64_t scale_bytes, bytes;  // zeroed as one block: maxbits .. inv_scale
+};
+inline CondWs cond_ws(const CondCfg& cfg, bool backward, void* ws) {
+    const int KS = cfg.H / 32;
+    Carver c(ws);
+    CondWs w;
+    w.maxbits = c.take<unsigned>(1, 256);
+    w.inv_scale = c.take<float>(1, 4);
+    w.scale_bytes = c.bytes();
+    w.gmax = c.take<unsigned>(1, 4);
+    c.reserve(256 - c.bytes());  // the rest of the 256-byte head
+    w.pimg = c.take<u4>(cfg.T * (int64_t)(KS * 128 + 4), 256);
+    w.timg = c.take<u4>(backward ? (cfg.T / 2) * (int64_t)(KS * 256) : 0, 16);
+    w.bytes = c.bytes();
+    return w;
+}
+// saved activations of the training forward: Affine inputs (S, M, D) | the coupling nets' (2S, M, 3 D/2 + 32 L)
+struct CondActs {
+    float *aff, *c;
+    int64_t floats;
+};
+inline CondActs cond_acts(int64_t M, int D, int S, int L, float* acts) {
+    Carver c(acts);
+    float* aff = c.take<float>((int64_t)S * M * D, 4);  // D = 32 / 64: every region is whole 16-byte units
+    float* nets = c.take<float>(2 * (int64_t)S * M * (3 * (D / 2) + 32 * L), 4);
+    return {aff, nets, c.bytes() / 4};
+}
+// deltas of every layer: Affine (2S, M, D) | coupling nets (2S, M, D + 32 L) | the pre-split h image of the g_W kernel
+// (H floats per context, 32-context groups; read as u4: 16-byte aligned, every region before it is whole 16-byte units)
+struct CondDeltas {
+    float *aff, *c, *himg;
+    int64_t floats;
+};
+inline CondDeltas cond_deltas(int64_t M, int D, int S, int L, int H, float* deltas) {
+    Carver c(deltas);
+    float* aff = c.take<float>(2 * (int64_t)S * M * D, 4);
+    float* nets = c.take<float>(2 * (int64_t)S * M * (D + 32 * L), 4);
+    float* himg = c.take<float>(((M + 31) / 32) * 32 * (int64_t)H, 4);
+    return {aff, nets, himg, c.bytes() / 4};
+}
+int launch_cond_image(const float* W, const float* b, int64_t ldw, const CondCfg& cfg, const CondWs& w, int backward_order,
+                      hipStream_t st);
 
 
 }  // namespace tnf

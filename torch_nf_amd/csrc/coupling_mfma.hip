@@ -549,12 +549,6 @@ flow_fold_apply_kernel(const float* z, float* z_out, float* __restrict__ sld, co
     for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < N; n += (int64_t)gridDim.x * 256) sld[m * N + n] += c;
 }
 
-static int64_t fb_head_bytes(int64_t Mp, int D) { return (((Mp * 2 * D + Mp + D + 1) * 4 + 15) / 16) * 16; }
-int64_t flow_forward_batch_workspace(int64_t Mp, int D, int S, int L) {
-    // fold (Mp, 2, D) | ldc (Mp) | rstd (D) | ld_bn (1) | moments (2 D + 2 doubles) | operand images (Mp, 2S, image)
-    return fb_head_bytes(Mp, D) + (2 * (int64_t)D + 2) * 8 + Mp * 2 * S * mfma_image_floats(D, L) * 4;
-}
-
 // The chain in steps, so that a sample-sharded caller can put a collective between a layer's local moments and the
 // statistics derived from them (one all-reduce of [sum, sum of squares, count] per BatchNorm layer):
 //   begin                    operand images of every layer (workspace)
@@ -565,31 +559,36 @@ int64_t flow_forward_batch_workspace(int64_t Mp, int D, int S, int L) {
 //                            for the next layer's load stage, constant log-det
 //   end                      the last fold as an elementwise pass; sum_log_det += constant log-dets
 // tnf_flow_forward_batch_f32 is exactly begin, (layer, fold) x 2S, end with the local moments.
+// fold (Mp, 2, D) | ldc (Mp) | rstd (D) | ld_bn (1) | moments (2 D + 2 doubles) | operand images (Mp, 2S, image)
 struct FbWs {
     float *fold, *ldc, *rstd, *ld_bn, *images;
     double* moments;
+    int64_t bytes;
 };
-static FbWs fb_ws(void* ws, int64_t Mp, int D) {
+static FbWs fb_ws(int64_t Mp, int D, int S, int L, void* ws) {
+    Carver c(ws);
     FbWs w;
-    w.fold = reinterpret_cast<float*>(ws);
-    w.ldc = w.fold + Mp * 2 * D;
-    w.rstd = w.ldc + Mp;
-    w.ld_bn = w.rstd + D;
-    w.moments = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + fb_head_bytes(Mp, D));
-    w.images = reinterpret_cast<float*>(w.moments + 2 * D + 2);
+    w.fold = c.take<float>(Mp * 2 * D, 16);
+    w.ldc = c.take<float>(Mp, 4);
+    w.rstd = c.take<float>(D, 4);
+    w.ld_bn = c.take<float>(1, 4);
+    w.moments = c.take<double>(2 * (int64_t)D + 2, 16);
+    w.images = c.take<float>(Mp * 2 * S * mfma_image_floats(D, L), 16);
+    w.bytes = c.bytes();
     return w;
 }
+int64_t flow_forward_batch_workspace(int64_t Mp, int D, int S, int L) { return fb_ws(Mp, D, S, L, nullptr).bytes; }
 
 int flow_forward_batch_begin(const float* params, int64_t Mp, int D, int S, int L, int U, int64_t pstride, void* ws,
                              hipStream_t st) {
     if (!mfma_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "flow_forward_batch: D=%d L=%d U=%d", D, L, U);
-    return launch_flow_images(params, fb_ws(ws, Mp, D).images, Mp, D, S, L, U, pstride, st);
+    return launch_flow_images(params, fb_ws(Mp, D, S, L, ws).images, Mp, D, S, L, U, pstride, st);
 }
 
 int flow_forward_batch_layer(int c, const float* z_in, const float* params, float* z_out, float* sum_log_det,
                              double* moments, int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U, int64_t pstride,
                              void* ws, hipStream_t st) {
-    const FbWs w = fb_ws(ws, Mp, D);
+    const FbWs w = fb_ws(Mp, D, S, L, ws);
     const FlowLayout fl = flow_layout(D, S, L, U);
     const int64_t img_floats = mfma_image_floats(D, L);
     if (!moments) moments = w.moments;
@@ -614,7 +613,7 @@ int flow_forward_batch_layer(int c, const float* z_in, const float* params, floa
 int flow_forward_batch_fold(int c, const float* params, const double* moments, float* bn_mean_out, float* bn_alpha_out,
                             int64_t Mp, int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st,
                             int real_D) {
-    const FbWs w = fb_ws(ws, Mp, D);
+    const FbWs w = fb_ws(Mp, D, S, L, ws);
     const FlowLayout fl = flow_layout(D, S, L, U);
     if (!moments) moments = w.moments;
     if (real_D)  // an embedded flow: BatchNorm over a padded column is not the identity (flow_pad_batch.hip)
@@ -627,10 +626,10 @@ int flow_forward_batch_fold(int c, const float* params, const double* moments, f
     return check_launch("flow_forward_batch_fold");
 }
 
-int flow_forward_batch_end(float* z_out, float* sum_log_det, int64_t M, int64_t Mp, int64_t N, int D, void* ws,
-                           hipStream_t st) {
+int flow_forward_batch_end(float* z_out, float* sum_log_det, int64_t M, int64_t Mp, int64_t N, int D, int S, int L,
+                           void* ws, hipStream_t st) {
     if (N <= 0) return TNF_OK;
-    const FbWs w = fb_ws(ws, Mp, D);
+    const FbWs w = fb_ws(Mp, D, S, L, ws);
     int64_t nb = (N * D / 4 + 255) / 256;
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(flow_fold_apply_kernel, grid_xm(nb, M), dim3(256), 0, st, z_out, z_out, sum_log_det, w.fold, w.ldc, Mp,
@@ -652,7 +651,7 @@ int launch_flow_forward_batch(const float* omega, const float* params, float* z_
         rc = flow_forward_batch_fold(c, params, nullptr, bn_mean_out, bn_alpha_out, Mp, D, S, L, U, pstride, eps, ws, st);
         if (rc) return rc;
     }
-    return flow_forward_batch_end(z_out, sum_log_det, M, Mp, N, D, ws, st);
+    return flow_forward_batch_end(z_out, sum_log_det, M, Mp, N, D, S, L, ws, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -800,11 +799,32 @@ fold_bwd_apply_kernel(const float* g_in, const float* __restrict__ v, const floa
     }
 }
 
+// the backward's workspace: PQ (Mp, 2, D) | S (Mp) | max |upstream gradient| (1) | racc (2 D + 1) | kk (2 D) | images |
+// 2 x g buffers (M, N, D)
+struct FtBwdWs {
+    float *PQ, *Ssum, *racc, *kk, *images, *gbuf[2];
+    unsigned* gmax;
+    int64_t zeroed_bytes, bytes;  // zeroed as one block: PQ .. racc
+};
+static FtBwdWs ft_bwd_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, void* ws) {
+    Carver c(ws);
+    FtBwdWs w;
+    w.PQ = c.take<float>(Mp * 2 * D, 256);
+    w.Ssum = c.take<float>(Mp, 4);
+    w.gmax = c.take<unsigned>(1, 4);
+    w.racc = c.take<float>(2 * D + 1, 4);  // [g_r part (D) | g_mu part (D) | sum S (1)]
+    w.zeroed_bytes = c.bytes();
+    w.kk = c.take<float>(2 * D, 4);
+    w.images = c.take<float>(Mp * 2 * S * mfma_image_floats(D, L), 256);  // 2S x an even number of 64-byte rows: whole 256s
+    w.gbuf[0] = c.take<float>(M * N * D, 256);
+    w.gbuf[1] = c.take<float>(M * N * D, 256);
+    c.reserve(256);  // slack: the published size has always carried one spare 256-byte block behind the last region
+    w.bytes = c.bytes(256);
+    return w;
+}
+
 int64_t flow_forward_train_workspace(int64_t M, int64_t Mp, int64_t N, int D, int S, int L) {
-    // forward: as flow_forward_batch.  backward: PQ (Mp, 2, D) | S (Mp) | kk (2 D) | images | 2 x g buffers (M, N, D)
-    const int64_t fwd = flow_forward_batch_workspace(Mp, D, S, L);
-    const int64_t bwd = (((Mp * 2 * D + Mp + 1 + 4 * D + 1) * 4 + 255) / 256) * 256 + Mp * 2 * S * mfma_image_floats(D, L) * 4 +
-                        2 * (((M * N * D * 4) + 255) / 256) * 256 + 256;
+    const int64_t fwd = fb_ws(Mp, D, S, L, nullptr).bytes, bwd = ft_bwd_ws(M, Mp, N, D, S, L, nullptr).bytes;
     return fwd > bwd ? fwd : bwd;
 }
 
@@ -814,7 +834,7 @@ int launch_flow_forward_train_fwd(const float* omega, const float* params, float
                                   int real_D) {
     if (!mfma_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "flow_forward_train: D=%d L=%d U=%d", D, L, U);
     if (N <= 0) return TNF_OK;
-    const FbWs w = fb_ws(ws, Mp, D);
+    const FbWs w = fb_ws(Mp, D, S, L, ws);
     float *ldc = w.ldc, *images = w.images;
     double* sums = w.moments;
     const FlowLayout fl = flow_layout(D, S, L, U);
@@ -863,19 +883,11 @@ int launch_flow_forward_train_bwd(const float* omega, const float* params, const
                                   int U, int64_t pstride, int64_t gpstride, void* ws, hipStream_t st) {
     if (!mfma_supported(D, L, U)) return fail(TNF_EUNSUPPORTED, "flow_forward_train: D=%d L=%d U=%d", D, L, U);
     if (N <= 0) return TNF_OK;
-    char* wsb = reinterpret_cast<char*>(ws);
-    float* PQ = reinterpret_cast<float*>(wsb);
-    float* Ssum = PQ + Mp * 2 * D;
-    unsigned* gmaxw = reinterpret_cast<unsigned*>(Ssum + Mp);  // max |upstream gradient|, for the split-f16 layer kernels
-    float* racc = Ssum + Mp + 1;  // [g_r part (D) | g_mu part (D) | sum S (1)]
-    float* kk = racc + 2 * D + 1;
-    const int64_t head = (((Mp * 2 * D + Mp + 1 + 4 * D + 1) * 4 + 255) / 256) * 256;
-    float* images = reinterpret_cast<float*>(wsb + head);
+    const FtBwdWs w = ft_bwd_ws(M, Mp, N, D, S, L, ws);
+    float *PQ = w.PQ, *Ssum = w.Ssum, *racc = w.racc, *kk = w.kk, *images = w.images, *const *gbuf = w.gbuf;
+    unsigned* gmaxw = w.gmax;  // max |upstream gradient|, for the split-f16 layer kernels
     const int nl = 2 * S;
     const int64_t img_floats = mfma_image_floats(D, L), plane = M * N * D;
-    const int64_t gb = ((plane * 4 + 255) / 256) * 256;
-    char* gbase = wsb + head + ((Mp * nl * img_floats * 4 + 255) / 256) * 256;
-    float* gbuf[2] = {reinterpret_cast<float*>(gbase), reinterpret_cast<float*>(gbase + gb)};
     const FlowLayout fl = flow_layout(D, S, L, U);
     int rc = launch_flow_images(params, images, Mp, D, S, L, U, pstride, st);
     if (rc) return rc;
@@ -889,7 +901,7 @@ int launch_flow_forward_train_bwd(const float* omega, const float* params, const
     const int64_t rpb = (N + sb - 1) / sb;
     const double rows = (double)M * (double)N;
     // ---- the last fold (behind layer nl-1): sums over (g_z, v), then g_v ----
-    if (hipMemsetAsync(PQ, 0, (size_t)(Mp * 2 * D + Mp + 1 + 2 * D + 1) * sizeof(float), st) != hipSuccess)  // .. racc
+    if (hipMemsetAsync(PQ, 0, (size_t)w.zeroed_bytes, st) != hipSuccess)
         return fail(TNF_ELAUNCH, "flow_forward_train_bwd: memset failed");
     rc = launch_gmax(g_z, M * N * D, gmaxw, st);
     if (rc) return rc;

@@ -440,13 +440,23 @@ bool wide_bwd_supported(int D, int L, int U) {
 
 static int64_t wide_bwd_chunks(int64_t N) { return (N + kWideBwdChunk - 1) / kWideBwdChunk; }
 
+// workspace of both wide backwards: [transposed image (MAF only) | records of one chunk | partial rows (chunk, slice, P)]
+struct WideBwdWs {
+    float *timg, *rec, *partials;
+    int64_t bytes;
+};
+static WideBwdWs wide_bwd_ws(int64_t N, int64_t timg_floats, const WideRec& rc, int64_t P, void* ws) {
+    const int64_t chunk = N < kWideBwdChunk ? N : kWideBwdChunk;
+    Carver c(ws);
+    float* timg = c.take<float>(timg_floats, 16);
+    float* rec = c.take<float>(((chunk + 15) / 16) * rc.blocks() * 256, 16);
+    float* partials = c.take<float>(wide_bwd_chunks(N) * kWideBwdSlices * P, 16);
+    return {timg, rec, partials, c.bytes()};
+}
+
 int64_t wide_bwd_workspace(int64_t N, int D, int L, int U) {
     const WideLayout wl = wide_layout(D, L, U);
-    const WideRec rc{wl.UT, wl.HT, L};
-    const int64_t chunk = N < kWideBwdChunk ? N : kWideBwdChunk;
-    const int64_t rec = ((chunk + 15) / 16) * rc.blocks() * 1024;
-    const int64_t P = coupling_num_params(D, L, U, 1);
-    return rec + wide_bwd_chunks(N) * kWideBwdSlices * P * 4;
+    return wide_bwd_ws(N, 0, WideRec{wl.UT, wl.HT, L}, coupling_num_params(D, L, U, 1), nullptr).bytes;
 }
 
 // One shared parameter row (M_p = 1); N = all samples of the call (M batches of one row are one batch).
@@ -462,10 +472,8 @@ int launch_coupling_backward_wide(const float* z, const float* params, const flo
     const WideRec rc{wl.UT, wl.HT, L};
     const size_t smem = (size_t)(wl.floats() + bl.floats()) * sizeof(float);
     const int64_t P = coupling_num_params(D, L, U, upper);
-    const int64_t chunk = N < kWideBwdChunk ? N : kWideBwdChunk;
-    char* wsb = reinterpret_cast<char*>(ws);
-    float* rec = reinterpret_cast<float*>(wsb);
-    float* partials = reinterpret_cast<float*>(wsb + ((chunk + 15) / 16) * rc.blocks() * 1024);
+    const WideBwdWs w = wide_bwd_ws(N, 0, rc, coupling_num_params(D, L, U, 1), ws);
+    float *rec = w.rec, *partials = w.partials;
     const int64_t nchunks = wide_bwd_chunks(N);
     for (int64_t ci = 0; ci < nchunks; ++ci) {
         WideBwdArgs a{z, params, g_zout, g_ld, g_z, rec, partials + ci * kWideBwdSlices * P, N, ci * kWideBwdChunk,
@@ -754,14 +762,10 @@ bool maf_wide_bwd_supported(int D, int L, int U) {
 
 static int64_t maf_num_params_(int D, int L, int U) { return 2 * (2 * (int64_t)D * U + (int64_t)(L - 1) * U * U); }
 
-// workspace: [transposed image | records of one chunk | partial rows]
 int64_t maf_wide_bwd_workspace(int64_t N, int D, int L, int U) {
     const MafLayout wl = maf_wide_layout(D, L, U);
     const WideBwdLayout bl{wl.UT, wl.DT, L};
-    const WideRec rc{wl.UT, wl.DT, L};
-    const int64_t chunk = N < kWideBwdChunk ? N : kWideBwdChunk;
-    return (int64_t)bl.floats() * 4 + ((chunk + 15) / 16) * rc.blocks() * 1024 +
-           wide_bwd_chunks(N) * kWideBwdSlices * maf_num_params_(D, L, U) * 4;
+    return wide_bwd_ws(N, bl.floats(), WideRec{wl.UT, wl.DT, L}, maf_num_params_(D, L, U), nullptr).bytes;
 }
 
 int launch_maf_backward_wide(const float* z, const float* params, const float* masks, const float* g_zout, const float* g_ld,
@@ -775,11 +779,8 @@ int launch_maf_backward_wide(const float* z, const float* params, const float* m
     const WideRec rc{wl.UT, wl.DT, L};
     const size_t smem = (size_t)wl.floats() * sizeof(float);
     const int64_t P = maf_num_params_(D, L, U);
-    const int64_t chunk = N < kWideBwdChunk ? N : kWideBwdChunk;
-    char* wsb = reinterpret_cast<char*>(ws);
-    float* timg = reinterpret_cast<float*>(wsb);
-    float* rec = reinterpret_cast<float*>(wsb + (int64_t)bl.floats() * 4);
-    float* partials = reinterpret_cast<float*>(wsb + (int64_t)bl.floats() * 4 + ((chunk + 15) / 16) * rc.blocks() * 1024);
+    const WideBwdWs w = wide_bwd_ws(N, bl.floats(), rc, P, ws);
+    float *timg = w.timg, *rec = w.rec, *partials = w.partials;
     hipLaunchKernelGGL(maf_bwd_timage_kernel, dim3((unsigned)(bl.floats() / 256)), dim3(64), 0, st, params, masks, timg, bl, D, U);
     const int64_t nchunks = wide_bwd_chunks(N);
     for (int64_t ci = 0; ci < nchunks; ++ci) {

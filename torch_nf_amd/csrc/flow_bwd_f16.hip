@@ -1224,31 +1224,40 @@ static int64_t rev_blocks_x(int64_t M, int64_t N, bool pair) {
 // workspace: [rimg | g_fold (Mp, 2S, 2, D) + glp_sum (Mp) + gmax (1) + overflow (1) | glp partials | partial rows];
 // g_fold .. overflow are zeroed by the backward
 struct RevWs {
-    int64_t rimg, gfold, glpp, part, total, nred;
+    float *rimg, *gfold, *glp_sum, *glpp;
+    unsigned* gmax;
+    int *overflow, *part;
+    int64_t zeroed_bytes, bytes;  // zeroed as one block: gfold .. overflow
 };
-static RevWs rev_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U) {
+static RevWs rev_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U, void* ws) {
+    Carver c(ws);
     RevWs w;
     const int H = D / 2;
     const int64_t P = 2 * (H * U + U) + (int64_t)(L - 1) * 2 * (U * U + U) + 2 * (U * H + H);
     const int64_t bx0 = rev_blocks_x(M, N > 0 ? N : 1, false), bx1 = rev_blocks_x(M, N > 0 ? N : 1, true);
-    w.nred = (Mp == 1 ? M : 1) * (bx0 > bx1 ? bx0 : bx1);  // workgroups that add into one gradient row (either kernel)
-    w.rimg = 0;
-    w.gfold = ((Mp * 2 * S * rev_image_floats(D, L) * 4 + 255) / 256) * 256;
-    w.glpp = w.gfold + ((Mp * 2 * S * 2 * D + Mp + 2) * 4 + 255) / 256 * 256;
-    w.part = w.glpp + ((Mp * w.nred * 4 + 255) / 256) * 256;
-    w.total = w.part + ((Mp * w.nred * 2 * S * (P + 2 * D) * 4 + 255) / 256) * 256;
+    const int64_t nred = (Mp == 1 ? M : 1) * (bx0 > bx1 ? bx0 : bx1);  // workgroups that add into one gradient row (either kernel)
+    w.rimg = c.take<float>(Mp * 2 * S * rev_image_floats(D, L), 256);
+    const int64_t zeroed_from = c.bytes(256);
+    w.gfold = c.take<float>(Mp * 2 * S * 2 * D, 256);
+    w.glp_sum = c.take<float>(Mp, 4);
+    w.gmax = c.take<unsigned>(1, 4);
+    w.overflow = c.take<int>(1, 4);
+    w.zeroed_bytes = c.bytes() - zeroed_from;
+    w.glpp = c.take<float>(Mp * nred, 256);
+    w.part = c.take<int>(Mp * nred * 2 * S * (P + 2 * D), 256);
+    w.bytes = c.bytes(256);
     return w;
 }
 int64_t flow_train_rev_workspace(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U) {
     // one shared parameter row: the M * N samples are one batch (launch_flow_bwd_rev), so the partial rows do not grow with M
-    if (Mp == 1 && M > 1) return rev_ws(1, 1, M * N, D, S, L, U).total;
-    return rev_ws(M, Mp, N, D, S, L, U).total;
+    if (Mp == 1 && M > 1) return rev_ws(1, 1, M * N, D, S, L, U, nullptr).bytes;
+    return rev_ws(M, Mp, N, D, S, L, U, nullptr).bytes;
 }
 
 template <int H, int L>
 static int launch_rev(const float* z0, const float* params, const float* bn_mean, const float* bn_alpha,
                       const float* g_lp, float* g_z, float* g_params, int64_t M, int64_t Mp, int64_t N, int S, int U,
-                      int64_t pstride, int64_t gpstride, char* ws, int* overflow_out, hipStream_t st) {
+                      int64_t pstride, int64_t gpstride, void* ws, int* overflow_out, hipStream_t st) {
     constexpr int D = 2 * H;
     typedef RevImage<H, L> R;
     static_assert(R::FLOATS % 4 == 0, "image is copied in 16-byte units");
@@ -1258,13 +1267,11 @@ static int launch_rev(const float* z0, const float* params, const float* bn_mean
         pair_lds_bytes(D, S, L) != PairLds<H, L>::floats(2 * S) * 4)
         return fail(TNF_ELAUNCH, "flow_bwd_f16: LDS size mismatch");
     const bool pair = rev_use_pair(D, S, L, U);
-    const RevWs w = rev_ws(M, Mp, N, D, S, L, U);
-    float* rimg = reinterpret_cast<float*>(ws + w.rimg);
-    float* gfold = reinterpret_cast<float*>(ws + w.gfold);
-    float* glp_sum = gfold + Mp * 2 * S * 2 * D;
-    unsigned* gmax = reinterpret_cast<unsigned*>(glp_sum + Mp);
-    int* overflow = reinterpret_cast<int*>(gmax + 1);
-    if (hipMemsetAsync(gfold, 0, (size_t)(Mp * 2 * S * 2 * D + Mp + 2) * sizeof(float), st) != hipSuccess)
+    const RevWs w = rev_ws(M, Mp, N, D, S, L, U, ws);
+    float *rimg = w.rimg, *gfold = w.gfold, *glp_sum = w.glp_sum;
+    unsigned* gmax = w.gmax;
+    int* overflow = w.overflow;
+    if (hipMemsetAsync(gfold, 0, (size_t)w.zeroed_bytes, st) != hipSuccess)
         return fail(TNF_ELAUNCH, "flow_bwd_f16: memset failed");
     hipLaunchKernelGGL((flow_rev_images_kernel<H, L>), grid_xm(2 * S, Mp), dim3(64), 0, st, params, bn_mean, bn_alpha,
                        rimg, S, U, pstride, Mp, pair ? 4.f : 1.f);
@@ -1287,7 +1294,7 @@ static int launch_rev(const float* z0, const float* params, const float* bn_mean
     if (fbits < 0) fbits = 0;
     const float fx = ldexpf(1.f, fbits);
     FlowBwdArgs a{z0, g_lp, rimg, gmax, g_z, g_params, gfold, glp_sum, M, Mp, N, gpstride, fl.stage, fl.p_up, S, U, fx,
-                  reinterpret_cast<int*>(ws + w.part), reinterpret_cast<float*>(ws + w.glpp), overflow};
+                  w.part, w.glpp, overflow};
     // the partial rows are indexed by this launch's own grid; the reduction reads as many
     const int64_t nred = (Mp == 1 ? M : 1) * bx;
     int rc = dispatch_bool(U <= 15, [&](auto spare) {
@@ -1305,7 +1312,7 @@ static int launch_rev(const float* z0, const float* params, const float* bn_mean
         const int P = 2 * (H_ * U + U) + (L - 1) * 2 * (U * U + U) + 2 * (U * H_ + H_);
         const int64_t prow = (int64_t)2 * S * (P + 2 * D);
         hipLaunchKernelGGL(flow_bwd_reduce_kernel, grid_xm((prow + 255) / 256, Mp), dim3(256), 0, st,
-                           reinterpret_cast<const int*>(ws + w.part), reinterpret_cast<const float*>(ws + w.glpp), gmax, overflow,
+                           w.part, w.glpp, gmax, overflow,
                            g_params, gfold, glp_sum, nred, 2 * S, P, D, gpstride, fl.stage, fl.p_up, fx, Mp, pair ? 1 : 0, U, L);
         rc = check_launch("flow_bwd_reduce");
         if (rc) return rc;
@@ -1325,9 +1332,8 @@ int launch_flow_bwd_rev(const float* z0, const float* params, const float* bn_me
         N *= M;
         M = 1;
     }
-    char* wsb = reinterpret_cast<char*>(ws);
     return dispatch_hl(D, L, [&](auto h, auto l) {
-        return launch_rev<h(), l()>(z0, params, bn_mean, bn_alpha, g_lp, g_z, g_params, M, Mp, N, S, U, pstride, gpstride, wsb,
+        return launch_rev<h(), l()>(z0, params, bn_mean, bn_alpha, g_lp, g_z, g_params, M, Mp, N, S, U, pstride, gpstride, ws,
                                     overflow_out, st);
     });
 }

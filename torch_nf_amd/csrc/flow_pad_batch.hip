@@ -108,27 +108,29 @@ static int launch_gather_stats(const float* mean, const float* alpha, float* mea
     return check_launch("flow_padded_batch_gather_stats");
 }
 
-static inline int64_t pb_round256(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
 // workspaces.  forward: [omega' | z' | params' | mean', alpha' | the chain's own]
 //              training: [omega' | g_z' | g_omega' | params' | g_params' | mean', alpha' | the pair's own]; its forward
 //              uses the same block with z' in the place of g_z'
 struct PadBatchWs {
-    int64_t o, z, go, p, gp, bn, inner, total;
+    float *o, *z, *go, *p, *gp, *mean, *alpha;  // go, gp: the training block only (empty regions otherwise)
+    char* inner;
+    int64_t bytes;
 };
-static PadBatchWs padbatch_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U, bool train) {
+static PadBatchWs padbatch_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U, bool train, void* ws) {
     const int W = 2 * padtrain_half(D);
-    const int64_t rows = pb_round256(M * N * W * 4), prow = pb_round256(Mp * flow_layout(W, S, L, U).total * 4);
+    const int64_t rows = M * N * W, prow = Mp * flow_layout(W, S, L, U).total;
+    Carver c(ws);
     PadBatchWs w;
-    w.o = 0;
-    w.z = w.o + rows;
-    w.go = w.z + rows;
-    w.p = w.go + (train ? rows : 0);
-    w.gp = w.p + prow;
-    w.bn = w.gp + (train ? prow : 0);
-    w.inner = w.bn + pb_round256((int64_t)2 * 2 * S * W * 4);
-    w.total = w.inner + pb_round256(train ? flow_forward_train_workspace(M, Mp, N > 0 ? N : 1, W, S, L)
-                                          : flow_forward_batch_workspace(Mp, W, S, L));
+    w.o = c.take<float>(rows, 256);
+    w.z = c.take<float>(rows, 256);
+    w.go = c.take<float>(train ? rows : 0, 256);
+    w.p = c.take<float>(prow, 256);
+    w.gp = c.take<float>(train ? prow : 0, 256);
+    w.mean = c.take<float>((int64_t)2 * S * W, 256);
+    w.alpha = c.take<float>((int64_t)2 * S * W, 4);
+    w.inner = c.take<char>(train ? flow_forward_train_workspace(M, Mp, N > 0 ? N : 1, W, S, L)
+                                 : flow_forward_batch_workspace(Mp, W, S, L), 256);
+    w.bytes = c.bytes(256);
     return w;
 }
 
@@ -141,12 +143,6 @@ static int padbatch_checks(const char* fn, int64_t M, int64_t Mp, int64_t N, int
     const int64_t need = flow_layout(D, S, L, U).total;
     if (pstride < need)
         return fail(TNF_EINVAL, "%s: params row has %lld elements, flow needs %lld", fn, (long long)pstride, (long long)need);
-    return TNF_OK;
-}
-
-static int padbatch_check_ws(const char* fn, const void* ws, int64_t ws_bytes, int64_t need) {
-    if (!ws || ws_bytes < need) return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)ws_bytes, (long long)need);
-    if (reinterpret_cast<uintptr_t>(ws) & 255u) return fail(TNF_EWORKSPACE, "%s: the workspace must be 256-byte aligned", fn);
     return TNF_OK;
 }
 
@@ -174,7 +170,7 @@ int tnf_flow_padded_batch_fold_f32(const float* params, const double* moments, f
     if (M_p < 1) return fail(TNF_EINVAL, "%s: M_p=%lld", fn, (long long)M_p);
     const int W = 2 * padtrain_half(D);
     if (!W) return fail(TNF_EUNSUPPORTED, "%s: no embedded layout for D=%d", fn, D);
-    if (reinterpret_cast<uintptr_t>(moments) & 7) return fail(TNF_EINVAL, "%s: moments must be 8-byte aligned", fn);
+    if (!is_aligned(moments, 8)) return fail(TNF_EINVAL, "%s: moments must be 8-byte aligned", fn);
     if (affine_off < 0 || (has_affine && pstride < affine_off + 2 * (int64_t)W))
         return fail(TNF_EINVAL, "%s: affine_off=%lld pstride=%lld", fn, (long long)affine_off, (long long)pstride);
     return launch_pad_finalize_fold(params, pstride, affine_off, moments, eps, mean_out, alpha_out, fold, ldc, M_p, W, D,
@@ -184,14 +180,14 @@ int tnf_flow_padded_batch_fold_f32(const float* params, const double* moments, f
 int64_t tnf_flow_padded_batch_workspace_bytes(int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t S, int32_t L, int32_t U) {
     const int64_t big = (int64_t)1 << 40;  // the row length is not this query's business
     if (int rc = padbatch_checks("tnf_flow_padded_batch_workspace_bytes", M, M_p, N, D, S, L, U, big)) return rc;
-    return padbatch_ws(M, M_p, N, D, S, L, U, false).total;
+    return padbatch_ws(M, M_p, N, D, S, L, U, false, nullptr).bytes;
 }
 
 int64_t tnf_flow_padded_batch_train_workspace_bytes(int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t S, int32_t L,
                                                     int32_t U) {
     const int64_t big = (int64_t)1 << 40;
     if (int rc = padbatch_checks("tnf_flow_padded_batch_train_workspace_bytes", M, M_p, N, D, S, L, U, big)) return rc;
-    return padbatch_ws(M, M_p, N, D, S, L, U, true).total;
+    return padbatch_ws(M, M_p, N, D, S, L, U, true, nullptr).bytes;
 }
 
 int tnf_flow_padded_forward_batch_f32(const float* omega, const float* params, float* z_out, float* sum_log_det,
@@ -205,18 +201,13 @@ int tnf_flow_padded_forward_batch_f32(const float* omega, const float* params, f
     if (!omega || !params || !z_out || !sum_log_det || !bn_mean_out || !bn_alpha_out)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
     if (z_out == omega) return fail(TNF_EINVAL, "%s: z_out must not alias omega", fn);
-    const PadBatchWs w = padbatch_ws(M, M_p, N, D, S, L, U, false);
-    if (int rc = padbatch_check_ws(fn, workspace, workspace_bytes, w.total)) return rc;
+    const PadBatchWs w = padbatch_ws(M, M_p, N, D, S, L, U, false, workspace);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, w.bytes, 256)) return rc;
     hipStream_t st = as_stream(stream);
     const int W = 2 * padtrain_half(D);
     const int64_t pe_stride = flow_layout(W, S, L, U).total;
-    char* ws = reinterpret_cast<char*>(workspace);
-    float* oe = reinterpret_cast<float*>(ws + w.o);
-    float* ze = reinterpret_cast<float*>(ws + w.z);
-    float* pe = reinterpret_cast<float*>(ws + w.p);
-    float* mean_e = reinterpret_cast<float*>(ws + w.bn);
-    float* alpha_e = mean_e + (int64_t)2 * S * W;
-    void* inner = ws + w.inner;
+    float *oe = w.o, *ze = w.z, *pe = w.p, *mean_e = w.mean, *alpha_e = w.alpha;
+    void* inner = w.inner;
     padbatch_count(TNF_PADBATCH_COUNT_FORWARD);
     int rc = launch_embed_rows(omega, oe, M * N, D, st);
     if (rc) return rc;
@@ -231,7 +222,7 @@ int tnf_flow_padded_forward_batch_f32(const float* omega, const float* params, f
         rc = flow_forward_batch_fold(c, pe, nullptr, mean_e, alpha_e, M_p, W, S, L, U, pe_stride, eps, inner, st, D);
         if (rc) return rc;
     }
-    rc = flow_forward_batch_end(ze, sum_log_det, M, M_p, N, W, inner, st);
+    rc = flow_forward_batch_end(ze, sum_log_det, M, M_p, N, W, S, L, inner, st);
     if (rc) return rc;
     rc = launch_gather_rows(ze, z_out, M * N, D, st);
     if (rc) return rc;
@@ -248,25 +239,20 @@ int tnf_flow_padded_forward_train_fwd_f32(const float* omega, const float* param
     if (M * N < 2) return fail(TNF_EINVAL, "%s: batch statistics need more than one row", fn);
     if (!omega || !params || !z_out || !sum_log_det || !states || !folds || !bn_mean_out || !bn_alpha_out)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (reinterpret_cast<uintptr_t>(states) & 15u) return fail(TNF_EINVAL, "%s: states must be 16-byte aligned", fn);
-    const PadBatchWs w = padbatch_ws(M, M_p, N, D, S, L, U, true);
-    if (int rc = padbatch_check_ws(fn, workspace, workspace_bytes, w.total)) return rc;
+    if (!is_aligned(states, 16)) return fail(TNF_EINVAL, "%s: states must be 16-byte aligned", fn);
+    const PadBatchWs w = padbatch_ws(M, M_p, N, D, S, L, U, true, workspace);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, w.bytes, 256)) return rc;
     hipStream_t st = as_stream(stream);
     const int W = 2 * padtrain_half(D);
     const int64_t pe_stride = flow_layout(W, S, L, U).total;
-    char* ws = reinterpret_cast<char*>(workspace);
-    float* oe = reinterpret_cast<float*>(ws + w.o);
-    float* ze = reinterpret_cast<float*>(ws + w.z);
-    float* pe = reinterpret_cast<float*>(ws + w.p);
-    float* mean_e = reinterpret_cast<float*>(ws + w.bn);
-    float* alpha_e = mean_e + (int64_t)2 * S * W;
+    float *oe = w.o, *ze = w.z, *pe = w.p, *mean_e = w.mean, *alpha_e = w.alpha;
     padbatch_count(TNF_PADBATCH_COUNT_TRAIN_FWD);
     int rc = launch_embed_rows(omega, oe, M * N, D, st);
     if (rc) return rc;
     rc = launch_embed_params(params, nullptr, nullptr, pe, nullptr, nullptr, M_p, D, S, L, U, pstride, st);
     if (rc) return rc;
     rc = launch_flow_forward_train_fwd(oe, pe, ze, sum_log_det, states, folds, mean_e, alpha_e, M, M_p, N, W, S, L, U,
-                                       pe_stride, eps, ws + w.inner, st, D);
+                                       pe_stride, eps, w.inner, st, D);
     if (rc) return rc;
     rc = launch_gather_rows(ze, z_out, M * N, D, st);
     if (rc) return rc;
@@ -285,20 +271,13 @@ int tnf_flow_padded_forward_train_bwd_f32(const float* omega, const float* param
     if (M * N < 2) return fail(TNF_EINVAL, "%s: batch statistics need more than one row", fn);
     if (!omega || !params || !states || !folds || !bn_mean || !bn_alpha || !g_z || !g_sum_log_det || !g_params)
         return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    if (reinterpret_cast<uintptr_t>(states) & 15u) return fail(TNF_EINVAL, "%s: states must be 16-byte aligned", fn);
-    const PadBatchWs w = padbatch_ws(M, M_p, N, D, S, L, U, true);
-    if (int rc = padbatch_check_ws(fn, workspace, workspace_bytes, w.total)) return rc;
+    if (!is_aligned(states, 16)) return fail(TNF_EINVAL, "%s: states must be 16-byte aligned", fn);
+    const PadBatchWs w = padbatch_ws(M, M_p, N, D, S, L, U, true, workspace);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, w.bytes, 256)) return rc;
     hipStream_t st = as_stream(stream);
     const int W = 2 * padtrain_half(D);
     const int64_t pe_stride = flow_layout(W, S, L, U).total;
-    char* ws = reinterpret_cast<char*>(workspace);
-    float* oe = reinterpret_cast<float*>(ws + w.o);
-    float* gze = reinterpret_cast<float*>(ws + w.z);
-    float* goe = g_omega ? reinterpret_cast<float*>(ws + w.go) : nullptr;
-    float* pe = reinterpret_cast<float*>(ws + w.p);
-    float* gpe = reinterpret_cast<float*>(ws + w.gp);
-    float* mean_e = reinterpret_cast<float*>(ws + w.bn);
-    float* alpha_e = mean_e + (int64_t)2 * S * W;
+    float *oe = w.o, *gze = w.z, *goe = g_omega ? w.go : nullptr, *pe = w.p, *gpe = w.gp, *mean_e = w.mean, *alpha_e = w.alpha;
     padbatch_count(TNF_PADBATCH_COUNT_TRAIN_BWD);
     int rc = launch_embed_rows(omega, oe, M * N, D, st);
     if (rc) return rc;
@@ -310,7 +289,7 @@ int tnf_flow_padded_forward_train_bwd_f32(const float* omega, const float* param
     if (hipMemsetAsync(gpe, 0, (size_t)(M_p * pe_stride) * sizeof(float), st) != hipSuccess)
         return fail(TNF_ELAUNCH, "%s: memset failed", fn);
     rc = launch_flow_forward_train_bwd(oe, pe, states, folds, mean_e, alpha_e, gze, g_sum_log_det, goe, gpe, M, M_p, N, W, S,
-                                       L, U, pe_stride, pe_stride, ws + w.inner, st);
+                                       L, U, pe_stride, pe_stride, w.inner, st);
     if (rc) return rc;
     rc = launch_gather_params(gpe, g_params, M_p, D, S, L, U, gpstride, st);
     if (rc) return rc;

@@ -108,9 +108,6 @@ __global__ void __launch_bounds__(256) padtrain_gather_params_kernel(const float
     if (k < fr.total) g_out[m * gpstride + k] = g[m * fe.total + padtrain_embed_index(k, D, H, L, U, fr, fe)];
 }
 
-static inline bool pt_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline int64_t pt_round256(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
 static unsigned rows_grid(int64_t R, int H) {
     const int64_t blocks = (R * (2 * H / 4) + 255) / 256;
     return (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));  // grid-stride beyond 32 workgroups per CU
@@ -158,19 +155,23 @@ int launch_gather_params(const float* g, float* g_out, int64_t Mp, int D, int S,
 
 // workspace of the composite: [z0' | g_z' | params' | g_params' | mean', alpha' | the backward's own]
 struct PadTrainWs {
-    int64_t z0, gz, p, gp, bn, rev, total;
+    float *z0, *gz, *p, *gp, *mean, *alpha;
+    char* rev;
+    int64_t bytes;
 };
-static PadTrainWs padtrain_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U) {
+static PadTrainWs padtrain_ws(int64_t M, int64_t Mp, int64_t N, int D, int S, int L, int U, void* ws) {
     const int W = 2 * padtrain_half(D);
-    const int64_t rows = pt_round256(M * N * W * 4), prow = pt_round256(Mp * flow_layout(W, S, L, U).total * 4);
+    const int64_t rows = M * N * W, prow = Mp * flow_layout(W, S, L, U).total;
+    Carver c(ws);
     PadTrainWs w;
-    w.z0 = 0;
-    w.gz = w.z0 + rows;
-    w.p = w.gz + rows;
-    w.gp = w.p + prow;
-    w.bn = w.gp + prow;
-    w.rev = w.bn + pt_round256((int64_t)2 * 2 * S * W * 4);
-    w.total = w.rev + flow_train_rev_workspace(M, Mp, N > 0 ? N : 1, W, S, L, U);
+    w.z0 = c.take<float>(rows, 256);
+    w.gz = c.take<float>(rows, 256);
+    w.p = c.take<float>(prow, 256);
+    w.gp = c.take<float>(prow, 256);
+    w.mean = c.take<float>((int64_t)2 * S * W, 256);
+    w.alpha = c.take<float>((int64_t)2 * S * W, 4);
+    w.rev = c.take<char>(flow_train_rev_workspace(M, Mp, N > 0 ? N : 1, W, S, L, U), 256);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -178,7 +179,7 @@ static int check_rows(const char* fn, const float* rows, const float* out, const
     if (!rows || !out) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
     if (R < 0) return fail(TNF_EINVAL, "%s: R=%lld", fn, (long long)R);
     if (!padtrain_half(D)) return fail(TNF_EUNSUPPORTED, "%s: no embedded layout for D=%d", fn, D);
-    if (!pt_aligned16(embedded)) return fail(TNF_EINVAL, "%s: the embedded rows must be 16-byte aligned", fn);
+    if (!is_aligned(embedded, 16)) return fail(TNF_EINVAL, "%s: the embedded rows must be 16-byte aligned", fn);
     return TNF_OK;
 }
 
@@ -261,7 +262,7 @@ static int padtrain_shape(const char* fn, int64_t M, int64_t M_p, int64_t N, int
 
 int64_t tnf_flow_padded_train_workspace_bytes(int64_t M, int64_t M_p, int64_t N, int32_t D, int32_t S, int32_t L, int32_t U) {
     if (int rc = padtrain_shape("tnf_flow_padded_train_workspace_bytes", M, M_p, N, D, S, L, U)) return rc;
-    return padtrain_ws(M, M_p, N, D, S, L, U).total;
+    return padtrain_ws(M, M_p, N, D, S, L, U, nullptr).bytes;
 }
 
 int tnf_flow_padded_log_prob_bwd_f32(const float* z0, const float* params, const float* bn_mean, const float* bn_alpha,
@@ -277,20 +278,13 @@ int tnf_flow_padded_log_prob_bwd_f32(const float* z0, const float* params, const
     if (gpstride < fr.total) return fail(TNF_EINVAL, "%s: g_params row too short", fn);
     if (N == 0) return TNF_OK;
     if (!z0 || !params || !bn_mean || !bn_alpha || !g_log_prob || !g_params) return fail(TNF_EINVAL, "%s: NULL pointer", fn);
-    const PadTrainWs w = padtrain_ws(M, M_p, N, D, S, L, U);
-    if (!workspace || workspace_bytes < w.total)
-        return fail(TNF_EWORKSPACE, "%s: workspace %lld < %lld", fn, (long long)workspace_bytes, (long long)w.total);
-    if (!pt_aligned16(workspace)) return fail(TNF_EINVAL, "%s: the workspace must be 16-byte aligned", fn);
+    const PadTrainWs w = padtrain_ws(M, M_p, N, D, S, L, U, workspace);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, w.bytes)) return rc;
+    if (!is_aligned(workspace, 16)) return fail(TNF_EINVAL, "%s: the workspace must be 16-byte aligned", fn);
     hipStream_t st = as_stream(stream);
     const int W = 2 * padtrain_half(D);
     const FlowLayout fe = flow_layout(W, S, L, U);
-    char* ws = reinterpret_cast<char*>(workspace);
-    float* z0e = reinterpret_cast<float*>(ws + w.z0);
-    float* gze = g_z ? reinterpret_cast<float*>(ws + w.gz) : nullptr;
-    float* pe = reinterpret_cast<float*>(ws + w.p);
-    float* gpe = reinterpret_cast<float*>(ws + w.gp);
-    float* mean_e = reinterpret_cast<float*>(ws + w.bn);
-    float* alpha_e = mean_e + (int64_t)2 * S * W;
+    float *z0e = w.z0, *gze = g_z ? w.gz : nullptr, *pe = w.p, *gpe = w.gp, *mean_e = w.mean, *alpha_e = w.alpha;
     padtrain_count(TNF_PADTRAIN_COUNT_BWD);
     int rc = launch_embed_rows(z0, z0e, M * N, D, st);
     if (rc) return rc;
@@ -300,7 +294,7 @@ int tnf_flow_padded_log_prob_bwd_f32(const float* z0, const float* params, const
     if (hipMemsetAsync(gpe, 0, (size_t)(M_p * fe.total) * sizeof(float), st) != hipSuccess)
         return fail(TNF_ELAUNCH, "%s: memset failed", fn);
     rc = launch_flow_bwd_rev(z0e, pe, mean_e, alpha_e, g_log_prob, gze, gpe, M, M_p, N, W, S, L, U, fe.total, fe.total,
-                             ws + w.rev, overflow, st);
+                             w.rev, overflow, st);
     if (rc) return rc;
     rc = launch_gather_params(gpe, g_params, M_p, D, S, L, U, gpstride, st);
     if (rc) return rc;

@@ -365,7 +365,7 @@ bn_normalize_kernel(const float* __restrict__ z, const float* __restrict__ mean,
 // returns true when the kernel also wrote the row count behind the sums (write_count asked for and the vector kernel ran)
 static bool launch_bn_sums(const float* z, double* sums, int64_t rows, int D, int64_t blocks, int64_t rpb, hipStream_t st,
                            int write_count = 0) {
-    const bool vec = (D % 4) == 0 && D <= 1024 && (reinterpret_cast<uintptr_t>(z) & 15) == 0;
+    const bool vec = (D % 4) == 0 && D <= 1024 && is_aligned(z, 16);
     if (vec) {
         const int rpi = 256 / (D / 4);
         // a streaming read: eight 16-byte loads per lane in flight, and few enough workgroups (two per CU) that
@@ -427,8 +427,8 @@ int launch_bn_normalize_from_moments(const float* z, const double* moments, floa
 
 int launch_bn_batch_forward(const float* z, float* z_out, float* mean_out, float* alpha_out,
                             float* log_det, int64_t rows, int D, float eps, void* ws, hipStream_t st) {
-    double* sums = reinterpret_cast<double*>(ws);
-    float* rstd = reinterpret_cast<float*>(sums + 2 * (size_t)D);
+    const BnBatchWs w = bn_batch_ws(D, ws);
+    double* const sums = w.sums;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * (size_t)D, st) != hipSuccess)
         return fail(TNF_ELAUNCH, "bn_batch_forward: memset failed");
     int64_t blocks = (rows + 255) / 256;
@@ -436,12 +436,12 @@ int launch_bn_batch_forward(const float* z, float* z_out, float* mean_out, float
     if (blocks < 1) blocks = 1;
     const int64_t rpb = (rows + blocks - 1) / blocks;
     launch_bn_sums(z, sums, rows, D, blocks, rpb, st);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(256), 0, st, sums, mean_out, alpha_out, rstd,
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(256), 0, st, sums, mean_out, alpha_out, w.rstd,
                        log_det, rows, D, eps);
     const int64_t total = rows * D;
     int64_t nb = (total + 255) / 256;
     if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(bn_normalize_kernel, dim3((unsigned)nb), dim3(256), 0, st, z, mean_out, rstd,
+    hipLaunchKernelGGL(bn_normalize_kernel, dim3((unsigned)nb), dim3(256), 0, st, z, mean_out, w.rstd,
                        z_out, D, total);
     return check_launch("bn_batch_forward");
 }

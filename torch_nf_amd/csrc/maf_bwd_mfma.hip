@@ -605,21 +605,21 @@ ar_fold_backward_kernel(const float* __restrict__ params, int64_t pstride, int64
     }
 }
 
-int launch_ar_flow_backward(const float* z, const float* params, const float* masks, const float* fold,
-                            const float* interval_consts, const float* g_lp, float* g_params, float* g_fold,
-                            float* glp_sum, int64_t M, int64_t Mp, int64_t N, int D, int L, int U, int64_t pstride,
-                            int64_t gpstride, hipStream_t st) {
+int launch_ar_flow_backward(const float* z, const float* params, const float* masks, const ArFlowWs& w,
+                            const float* interval_consts, const float* g_lp, float* g_params, int64_t M, int64_t Mp,
+                            int64_t N, int D, int L, int U, int64_t pstride, int64_t gpstride, hipStream_t st) {
     if (!maf_bwd_mfma_supported(D, L, U))
         return fail(TNF_EUNSUPPORTED, "ar_flow_backward: no kernel for D=%d L=%d U=%d", D, L, U);
     if (N <= 0) return TNF_OK;
-    if (hipMemsetAsync(g_fold, 0, (size_t)(Mp * 2 * D + Mp + 1) * sizeof(float), st) != hipSuccess)
+    float *fold = w.fold, *g_fold = w.g_fold, *glp_sum = w.glp_sum;
+    if (hipMemsetAsync(g_fold, 0, (size_t)w.zeroed_bytes, st) != hipSuccess)
         return fail(TNF_ELAUNCH, "ar_flow_backward: memset failed");
     MafBwdArgs a = {};
     a.z = z; a.params = params; a.masks = masks; a.g_params = g_params;
     a.M = M; a.Mp = Mp; a.N = N; a.pstride = pstride; a.gpstride = gpstride; a.D = D; a.L = L; a.U = U;
     a.pre = fold; a.iv = interval_consts; a.g_lp = g_lp; a.g_fold = g_fold; a.glp_sum = glp_sum;
     if (maf_bwd_nacc(D, L, U) == 1) {  // shared accumulators: fixed point, scaled by the largest upstream gradient
-        unsigned* gmax = reinterpret_cast<unsigned*>(glp_sum + Mp);
+        unsigned* gmax = w.gmax;
         const int64_t n = M * N;
         int64_t blocks = (n + 255) / 256;
         if (blocks > 256) blocks = 256;

@@ -725,14 +725,17 @@ enum { MOG_GENERIC_WGS = 512 };
 struct MogBwdPlan {
     bool fused;
     int G, rc;
-    int64_t blocks, area, partial_floats, ws_floats;
+    int64_t blocks, area;
     size_t smem;
+    float *partials, *areas;  // the workspace: partial rows (M, G, P) | the generic kernels' areas (blocks, area)
+    int64_t ws_bytes;
 };
-static MogBwdPlan mog_bwd_plan(const MogGeom& g, int D, int K) {
+static MogBwdPlan mog_bwd_plan(const MogGeom& g, int D, int K, void* ws) {
     MogBwdPlan p;
+    int64_t partial_floats = 0;
     const int64_t P = mog_P(D, K), LDP = mog_ldp(D, K);
     p.fused = !g_force_generic && mog_fused_supported(D, K);
-    p.G = 1, p.rc = 0, p.partial_floats = 0;
+    p.G = 1, p.rc = 0;
     if (g.shared) {
         int64_t G = (g.N + MOG_TILE - 1) / MOG_TILE;
         const int64_t cap = g.M >= 256 ? 1 : 256 / g.M;
@@ -740,7 +743,7 @@ static MogBwdPlan mog_bwd_plan(const MogGeom& g, int D, int K) {
         p.G = G < 1 ? 1 : (int)G;
         p.area = LDP + P + 2 * D + (int64_t)MOG_TILE * ((3 * D + 2) | 1);
         p.blocks = g.M * p.G;
-        if (p.G > 1) p.partial_floats = g.M * p.G * P;
+        if (p.G > 1) partial_floats = g.M * p.G * P;
     } else {
         const int64_t lanes = p.fused ? 0 : (int64_t)MOG_TILE * ((3 * D) | 1);
         int64_t rc = p.fused ? (MOG_LDS_FLOATS - 2 * D) / (2 * LDP) : 32768 / LDP;
@@ -758,7 +761,10 @@ static MogBwdPlan mog_bwd_plan(const MogGeom& g, int D, int K) {
         p.smem = 0;
         if (p.blocks > MOG_GENERIC_WGS) p.blocks = MOG_GENERIC_WGS;
     }
-    p.ws_floats = p.partial_floats + p.blocks * p.area;
+    Carver c(ws);
+    p.partials = c.take<float>(partial_floats, 16);
+    p.areas = c.take<float>(p.blocks * p.area, 4);
+    p.ws_bytes = c.bytes();
     return p;
 }
 
@@ -766,7 +772,7 @@ int64_t mog_bwd_workspace(int64_t M, int64_t Mp, int64_t N, int D, int K) {
     if (mog_num_params(D, K) < 0) return -1;
     const MogGeom g = mog_geom(M, Mp, N);
     if (g.M * g.N == 0) return 0;
-    return mog_bwd_plan(g, D, K).ws_floats * 4;
+    return mog_bwd_plan(g, D, K, nullptr).ws_bytes;
 }
 
 #define MOG_BWD_CASE(Dv, KERNEL, ...)                                                    \
@@ -795,10 +801,10 @@ int launch_mog_log_prob_backward(const float* z, const float* params, const floa
             return fail(TNF_ELAUNCH, "mog_log_prob_backward: memset failed");
         return TNF_OK;
     }
-    const MogBwdPlan pl = mog_bwd_plan(g, D, K);
+    const MogBwdPlan pl = mog_bwd_plan(g, D, K, ws);
     if (pl.blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "mog_log_prob_backward: grid too large");
     const dim3 grid((unsigned)pl.blocks);
-    float* areas = (float*)ws + pl.partial_floats;  // used by the generic kernels only
+    float* areas = pl.areas;  // used by the generic kernels only
     if (!g.shared) {
         MOG_BWD_SWITCH(mog_bwd_lane_kernel, z, params, bounds, g_lp, g_z, g_params, g.Mz, g.M, g.N, D, K, ld, pl.rc, areas,
                        pl.area)
@@ -808,7 +814,7 @@ int launch_mog_log_prob_backward(const float* z, const float* params, const floa
     const int G = pl.G;
     const int64_t ntiles = (g.N + MOG_TILE - 1) / MOG_TILE;
     const int64_t per = (ntiles + G - 1) / G;
-    float* partial = G == 1 ? g_params : (float*)ws;
+    float* partial = G == 1 ? g_params : pl.partials;
     MOG_BWD_SWITCH(mog_bwd_shared_kernel, z, params, bounds, g_lp, g_z, partial, g.Mz, g.Mp, g.M, g.N, D, K, ld, G, per,
                    areas, pl.area)
     if (pl.fused) mog_count(TNF_MOG_COUNT_LOGPROB_BWD);
@@ -816,7 +822,7 @@ int launch_mog_log_prob_backward(const float* z, const float* params, const floa
     if (rc || G == 1) return rc;
     const int64_t blocks = (g.M * P + 255) / 256;
     if (blocks > 0x7fffffff) return fail(TNF_EUNSUPPORTED, "mog_log_prob_backward: grid too large");
-    hipLaunchKernelGGL(mog_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, g_params, g.M, P, G);
+    hipLaunchKernelGGL(mog_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)pl.partials, g_params, g.M, P, G);
     return check_launch("mog_log_prob_backward (ordered sum)");
 }
 

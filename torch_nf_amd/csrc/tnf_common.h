@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include "../../include/tnf.h"
+#include "workspace.h"
 
 namespace tnf {
 
@@ -13,6 +14,8 @@ namespace tnf {
 char* err_buf();
 int fail(int code, const char* fmt, ...);
 int check_launch(const char* what);
+// EWORKSPACE unless `ws` holds `need` bytes on a multiple of `base_align` (the padded batch-statistics composites: 256)
+int check_workspace(const char* fn, const void* ws, int64_t ws_bytes, int64_t need, int base_align = 1);
 
 void diag_count(int family);  // api.hip: process-wide launch counters behind tnf_diag_launch_count
 
@@ -231,8 +234,8 @@ int flow_forward_batch_layer(int c, const float* z_in, const float* params, floa
 int flow_forward_batch_fold(int c, const float* params, const double* moments, float* bn_mean_out, float* bn_alpha_out,
                             int64_t Mp, int D, int S, int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st,
                             int real_D = 0);
-int flow_forward_batch_end(float* z_out, float* sum_log_det, int64_t M, int64_t Mp, int64_t N, int D, void* ws,
-                           hipStream_t st);
+int flow_forward_batch_end(float* z_out, float* sum_log_det, int64_t M, int64_t Mp, int64_t N, int D, int S, int L,
+                           void* ws, hipStream_t st);
 int launch_flow_forward_batch(const float* omega, const float* params, float* z_out, float* sum_log_det,
                               float* bn_mean_out, float* bn_alpha_out, int64_t M, int64_t Mp, int64_t N, int D, int S,
                               int L, int U, int64_t pstride, float eps, void* ws, hipStream_t st);
@@ -269,6 +272,18 @@ int launch_affine(int dtype, const void* z, const void* params, void* z_out, voi
                   hipStream_t st);
 int launch_bn_apply(int dtype, const void* z, const float* mean, const float* alpha, void* z_out,
                     float* log_det, int64_t rows, int D, int inverse, hipStream_t st);
+// workspace of the BatchNorm batch entries: sums (2 D doubles) | rstd (D)
+struct BnBatchWs {
+    double* sums;
+    float* rstd;
+    int64_t bytes;
+};
+inline BnBatchWs bn_batch_ws(int D, void* ws) {
+    Carver c(ws);
+    double* sums = c.take<double>(2 * (int64_t)D, 16);
+    float* rstd = c.take<float>(D, 4);
+    return {sums, rstd, c.bytes(16)};
+}
 int launch_bn_batch_forward(const float* z, float* z_out, float* mean_out, float* alpha_out,
                             float* log_det, int64_t rows, int D, float eps, void* ws, hipStream_t st);
 
@@ -403,10 +418,31 @@ int launch_maf_mfma(const MafArgs& a, hipStream_t st);
 int launch_ar_fold(const float* params, int64_t pstride, int64_t p_maf, const float* bn_mean, const float* bn_alpha,
                    float* fold, float* ldc, int64_t Mp, int D, int inverse, hipStream_t st);
 bool maf_bwd_mfma_supported(int D, int L, int U);
-int launch_ar_flow_backward(const float* z, const float* params, const float* masks, const float* fold,
-                            const float* interval_consts, const float* g_lp, float* g_params, float* g_fold,
-                            float* glp_sum, int64_t M, int64_t Mp, int64_t N, int D, int L, int U, int64_t pstride,
-                            int64_t gpstride, hipStream_t st);
+// workspace of the AR-flow entries: fold (Mp, 2, D) | ldc (Mp) and, for the backward, g_fold (Mp, 2, D) | glp_sum (Mp) |
+// max |g_log_prob| (1) -- those three zeroed as one block
+struct ArFlowWs {
+    float *fold, *ldc, *g_fold, *glp_sum;
+    unsigned* gmax;
+    int64_t zeroed_bytes, bytes;  // zeroed: g_fold .. gmax
+};
+inline ArFlowWs ar_flow_ws(int64_t Mp, int D, bool backward, void* ws) {
+    Carver c(ws);
+    ArFlowWs w = {};
+    w.fold = c.take<float>(Mp * 2 * D, 16);
+    w.ldc = c.take<float>(Mp, 4);
+    if (backward) {
+        const int64_t zeroed_from = c.bytes();
+        w.g_fold = c.take<float>(Mp * 2 * D, 4);
+        w.glp_sum = c.take<float>(Mp, 4);
+        w.gmax = c.take<unsigned>(1, 4);
+        w.zeroed_bytes = c.bytes() - zeroed_from;
+    }
+    w.bytes = c.bytes(16);
+    return w;
+}
+int launch_ar_flow_backward(const float* z, const float* params, const float* masks, const ArFlowWs& w,
+                            const float* interval_consts, const float* g_lp, float* g_params, int64_t M, int64_t Mp,
+                            int64_t N, int D, int L, int U, int64_t pstride, int64_t gpstride, hipStream_t st);
 int launch_maf_backward_mfma(const float* z, const float* params, const float* masks, const float* g_zout,
                              const float* g_ld, float* g_z, float* g_params, int64_t M, int64_t Mp, int64_t N, int D,
                              int L, int U, int64_t pstride, int64_t gpstride, hipStream_t st);
