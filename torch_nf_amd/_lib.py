@@ -240,6 +240,16 @@ PADBATCH_SIGNATURES = {
                                                              _i64, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _vp]),
 }
 
+# per-context coupling flows with fewer than 32 samples per context, one launch per call, declared in
+# include/tnf_ctxflow.h: an eighth table (tests/test_ctx_flow_host.py)
+CTXFLOW_SIGNATURES = {
+    "tnf_ctx_flow_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i64]),
+    "tnf_ctx_flow_launch_count": (_i64, [_i32]),
+    "tnf_ctx_flow_log_prob_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                                 _i64, _vp]),
+    "tnf_ctx_flow_forward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -250,7 +260,7 @@ def _load():
         )
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
-                  PADBATCH_SIGNATURES):
+                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

@@ -43,12 +43,19 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          per row, fusion AUTO or FLOW, flow_padded_train_supported
                                          (2 <= D <= 63 but 32: asked after train_reversible, whose
                                          widths it excludes, and before train_layers)
+  context_rows      forward (frozen),    context_rows (default off), coupling, plain, const stats,   ctxflow_ops.ctx_flow_
+                    log_prob, inverse    3-d, several parameter rows = the larger batch, M_z = 1 or  forward_raw, ctx_flow_
+                                         M (forward: M), 1 <= N <= 31, fusion AUTO or FLOW,          log_prob_raw
+                                         ctx_flow_supported, and not (log_prob or inverse at D = 64
+                                         with N <= 5: the per-layer composition is faster there,
+                                         DESIGN.md 18) (asked last: only calls that would otherwise
+                                         compose bijectors)
   bijectors         all                  everything else: the reference's loop, one kernel per       coupling, maf, affine,
                                          bijector                                                    bn_apply, bn_batch_forward
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
-a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, the batch-statistics
-chains (padded or not) and the per-layer chain do not.
+a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `context_rows`, the
+batch-statistics chains (padded or not) and the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
 Sampling: the base density is evaluated first (base_log_density_f64), except that `padded` and the whole-flow `fused`
@@ -59,7 +66,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, ops, padbatch_ops, padtrain_ops
+from . import _lib, ctxflow_ops, ops, padbatch_ops, padtrain_ops
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -289,6 +296,24 @@ class NormFlow(DensityEstimator):
                 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
                 and padbatch_ops.flow_padded_batch_supported(self.D, self.num_stages, self.num_layers, self.num_units))
 
+    def _context_rows_ok(self, op, z, params, facts):
+        """One launch for a per-context call with fewer than 32 samples per context (csrc/flow_ctx.hip): only with the
+        switch `context_rows` on, a coupling stack, plain, constant statistics, a 3-d z, several parameter rows that
+        are the larger batch, one block of z rows for all contexts or one per context (sampling: one per context), and
+        the fusion setting AUTO or FLOW as for the `padded` family.  One measured exception (DESIGN.md 18,
+        profiles/r14_ctxbench.txt): the inverse direction at D = 64 with at most 5 samples per context stays on the
+        composition, whose fp32-MFMA layer kernel is faster there (0.82 x at N = 1 .. 0.97 x at N = 4; 1.07 x at N = 6).
+        No gradients: calls under autograd keep their routes (a per-context whole-flow backward is a follow-up)."""
+        arch, shape, stats_graph, _, plain, _ = facts
+        if not (getattr(self, "context_rows", False) and arch == "coupling" and plain and not stats_graph
+                and z.dim() == 3 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
+            return False
+        M = params.size(0)
+        if op != "forward" and shape[0] == 64 and z.size(1) <= 5:
+            return False
+        return (M > 1 and z.size(0) in ((M,) if op == "forward" else (1, M))
+                and ctxflow_ops.ctx_flow_supported(*shape, z.size(1)))
+
     def _stats_in_graph(self):
         """Do the cached BatchNorm statistics still carry the graph of the batch-mode forward that produced them
         (per-bijector forward under autograd -- the reference's behaviour, bijectors.py:414-415)?  Then every later
@@ -368,6 +393,8 @@ class NormFlow(DensityEstimator):
             pair = self._train_path(z, params, stats_graph)
             if pair is not None:
                 return Route("train_" + pair, False, False)
+        if self._context_rows_ok(op, z, params, f):  # asked last: nothing another family takes changes hands
+            return Route("context_rows", False, False)
         return _BIJECTORS
 
     # -- sampling -----------------------------------------------------------
@@ -439,6 +466,8 @@ class NormFlow(DensityEstimator):
             elif family == "padded":  # no fused support layer: it runs below as its own kernel
                 z, sld, *written = ops.flow_padded_forward_raw(z, p_dev, *self._flow_args(),
                                                                want_log_q=route.writes_log_q)
+            elif family == "context_rows":  # one wave per context; the support layer as for `padded`
+                z, sld = ctxflow_ops.ctx_flow_forward_raw(z, p_dev, *self._flow_args())
             elif family == "fused":  # `written` stays None where the selected kernel variant has no log_q output
                 z, sld, *written = ops.flow_forward_raw(z, p_dev, *self._flow_args(), self.fusion, interval_consts=consts,
                                                         want_log_q=route.writes_log_q)
@@ -480,6 +509,9 @@ class NormFlow(DensityEstimator):
         if family == "padded":
             return ops.flow_padded_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
                                                 want_sld=want_sld)
+        if family == "context_rows":
+            return ctxflow_ops.ctx_flow_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
+                                                     want_sld=want_sld)
         return ops.flow_log_prob_raw(z, params, *self._flow_args(), self.fusion, want_lp=want_lp, want_z0=want_z0,
                                      want_sld=want_sld, interval_consts=consts)
 
@@ -529,7 +561,7 @@ class NormFlow(DensityEstimator):
             # support layer first (it is the last bijector of the stack), then the core's density:
             # log q(z) = log q_core(s^-1(z)) - log|det ds| -- same sum as density_estimator.py:395-416
             z, ld_support = self.bijectors[-1].inverse_and_log_det(z)
-        if family in ("ar_fused", "padded", "fused"):
+        if family in ("ar_fused", "padded", "fused", "context_rows"):
             log_q = self._fused_density(family, z, params, consts)[0]
         elif family == "ar_train":
             masks, mean, alpha, D, L, U = self._ar_args()
