@@ -30,7 +30,7 @@
  * tnf_set_launch_gate, so it can be captured into a HIP graph.
  * Included by tnf.h; a header of its own for the reason tnf_mog.h gives.  Bound by torch_nf_amd/_lib.py
  * CTXFLOW_SIGNATURES; tests/test_ctx_flow_host.py keeps this header, the exports and that table in step.
- * float32 only; no gradients (a per-context whole-flow backward is a follow-up). */
+ * float32 only; no gradients here: the backward of tnf_ctx_flow_log_prob_f32 from its z0 is tnf_ctxtrain.h. */
 #ifndef TNF_CTXFLOW_H
 #define TNF_CTXFLOW_H
 #include <stdint.h>

@@ -250,6 +250,15 @@ CTXFLOW_SIGNATURES = {
     "tnf_ctx_flow_forward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _vp]),
 }
 
+# the log_prob backward of those per-context flows, one launch per call, declared in include/tnf_ctxtrain.h: a ninth
+# table (tests/test_ctx_train_host.py)
+CTXTRAIN_SIGNATURES = {
+    "tnf_ctx_train_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i64]),
+    "tnf_ctx_train_launch_count": (_i64, []),
+    "tnf_ctx_train_log_prob_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
+                                                      _i64, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -260,7 +269,7 @@ def _load():
         )
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
-                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES):
+                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

@@ -43,6 +43,12 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          per row, fusion AUTO or FLOW, flow_padded_train_supported
                                          (2 <= D <= 63 but 32: asked after train_reversible, whose
                                          widths it excludes, and before train_layers)
+  train_context     log_prob             context_training (default off), coupling, float32, grad     ctxtrain_ops.ctx_flow_
+                                         mode on and params or z requires grad, const stats, 3-d,    log_prob_train
+                                         several parameter rows = the larger batch, M_z = M (or 1
+                                         when z does not require grad), 1 <= N <= 31, fusion AUTO or
+                                         FLOW, ctx_train_supported (asked after the training pairs
+                                         above: only calls that would otherwise compose bijectors)
   context_rows      forward (frozen),    context_rows (default off), coupling, plain, const stats,   ctxflow_ops.ctx_flow_
                     log_prob, inverse    3-d, several parameter rows = the larger batch, M_z = 1 or  forward_raw, ctx_flow_
                                          M (forward: M), 1 <= N <= 31, fusion AUTO or FLOW,          log_prob_raw
@@ -54,8 +60,8 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          bijector                                                    bn_apply, bn_batch_forward
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
-a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `context_rows`, the
-batch-statistics chains (padded or not) and the per-layer chain do not.
+a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `train_context`,
+`context_rows`, the batch-statistics chains (padded or not) and the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
 Sampling: the base density is evaluated first (base_log_density_f64), except that `padded` and the whole-flow `fused`
@@ -66,7 +72,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, ctxflow_ops, ops, padbatch_ops, padtrain_ops
+from . import _lib, ctxflow_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -303,7 +309,7 @@ class NormFlow(DensityEstimator):
         the fusion setting AUTO or FLOW as for the `padded` family.  One measured exception (DESIGN.md 18,
         profiles/r14_ctxbench.txt): the inverse direction at D = 64 with at most 5 samples per context stays on the
         composition, whose fp32-MFMA layer kernel is faster there (0.82 x at N = 1 .. 0.97 x at N = 4; 1.07 x at N = 6).
-        No gradients: calls under autograd keep their routes (a per-context whole-flow backward is a follow-up)."""
+        No gradients: calls under autograd keep their routes, or take `train_context` with its own switch on."""
         arch, shape, stats_graph, _, plain, _ = facts
         if not (getattr(self, "context_rows", False) and arch == "coupling" and plain and not stats_graph
                 and z.dim() == 3 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
@@ -313,6 +319,22 @@ class NormFlow(DensityEstimator):
             return False
         return (M > 1 and z.size(0) in ((M,) if op == "forward" else (1, M))
                 and ctxflow_ops.ctx_flow_supported(*shape, z.size(1)))
+
+    def _context_train_ok(self, z, params, facts):
+        """One launch each way for a per-context log_prob under autograd with fewer than 32 samples per context
+        (csrc/flow_ctx.hip forward keeping z0, csrc/flow_ctx_bwd.hip backward): only with the switch `context_training`
+        on (independent of `context_rows`), a coupling stack, float32, grad mode on and params or z requiring grad,
+        constant statistics, a 3-d z, several parameter rows that are the larger batch, one block of z per context --
+        or one shared block that requires no grad: its gradient would need a sum over contexts -- and the fusion setting
+        AUTO or FLOW as for the `padded` family."""
+        arch, shape, stats_graph, f32, _, _ = facts
+        if not (getattr(self, "context_training", False) and arch == "coupling" and f32 and torch.is_grad_enabled()
+                and (params.requires_grad or z.requires_grad) and not stats_graph and z.dim() == 3
+                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
+            return False
+        M = params.size(0)
+        return (M > 1 and (z.size(0) == M or (z.size(0) == 1 and not z.requires_grad))
+                and ctxtrain_ops.ctx_train_supported(*shape, z.size(1)))
 
     def _stats_in_graph(self):
         """Do the cached BatchNorm statistics still carry the graph of the batch-mode forward that produced them
@@ -393,6 +415,8 @@ class NormFlow(DensityEstimator):
             pair = self._train_path(z, params, stats_graph)
             if pair is not None:
                 return Route("train_" + pair, False, False)
+        if op == "log_prob" and self._context_train_ok(z, params, f):
+            return Route("train_context", False, False)
         if self._context_rows_ok(op, z, params, f):  # asked last: nothing another family takes changes hands
             return Route("context_rows", False, False)
         return _BIJECTORS
@@ -568,6 +592,8 @@ class NormFlow(DensityEstimator):
             log_q = ops.ar_flow_log_prob_train(z, params, masks, mean, alpha, consts, D, L, U)
         elif family == "train_padded":  # ... at 2 <= D <= 63 but 32: the reversible pair at the embedded width
             log_q = padtrain_ops.flow_padded_log_prob_train(z, params, *self._flow_args())
+        elif family == "train_context":  # ... per-context rows with fewer than 32 samples each: one launch each way
+            log_q = ctxtrain_ops.ctx_flow_log_prob_train(z, params, *self._flow_args())
         elif family != "bijectors":  # training with the BatchNorm statistics constant, one of the two fused pairs
             log_q = ops.flow_log_prob_train(z, params, *self._flow_args(), reversible=family == "train_reversible")
         else:
