@@ -638,4 +638,5 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
 #include "tnf_padbatch.h" /* sampling with fresh batch statistics at any D <= 63: a header and a table of its own */
 #include "tnf_ctxflow.h"  /* per-context flows with fewer than 32 samples each, one launch per call: the same */
 #include "tnf_ctxtrain.h" /* ... and their log_prob backward, one launch per call: the same */
+#include "tnf_sampletrain.h" /* training through frozen-statistics sampling in one backward kernel: the same */
 #endif /* TNF_H */

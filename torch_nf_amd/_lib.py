@@ -259,6 +259,16 @@ CTXTRAIN_SIGNATURES = {
                                                       _i64, _i64, _vp]),
 }
 
+# training through frozen-statistics sampling: the backward of the sampling pass in one walk kernel, declared in
+# include/tnf_sampletrain.h: a tenth table (tests/test_sample_train_host.py)
+SAMPLETRAIN_SIGNATURES = {
+    "tnf_flow_sample_train_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "tnf_flow_sample_train_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "tnf_sampletrain_launch_count": (_i64, []),
+    "tnf_flow_sample_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32,
+                                               _i32, _i64, _i64, _vp, _i64, _vp, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -269,7 +279,7 @@ def _load():
         )
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
-                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES):
+                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

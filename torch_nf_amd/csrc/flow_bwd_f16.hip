@@ -472,7 +472,9 @@ struct RegAccum {
 // points at this lane's [k0 | k1] constants (k1 at kc + D) of the batch-moment correction for the transformed
 // half: the upstream gradient is g + k0 + k1 y'.  MODE 2: an inverse-direction layer y' = (y - t) e^-s with its
 // INPUT saved; kmask != 0 with kc == NULL means "finalize": the upstream gradient of the transformed half is
-// gl_fin * y' (the base density's -g_log_prob y'), passed in kmask.
+// gl_fin * y' (the base density's -g_log_prob y'), passed in kmask.  MODE 3: the forward-direction layer
+// y' = t + y e^s of the sampling walk (flow_sample_bwd_kernel): y comes in as the layer's OUTPUT y' and leaves as its
+// input (y' - t) e^-s; the deltas are those of MODE 1 written on the output, d t = g, d s = g (y' - t) + gl.
 template <int H, int L, bool SPARE, int MODE, class ACCP>
 __device__ __forceinline__ void layer_bwd16(const float* img, ACCP& accp, float* scrA, float* scrB, int lane, int U,
                                             const f4 (&x)[(H + 15) / 16], f4 (&y)[(H + 15) / 16],
@@ -498,14 +500,37 @@ __device__ __forceinline__ void layer_bwd16(const float* img, ACCP& accp, float*
     for (int i = 0; i < 4; ++i) ident[i] = (4 * q + i == s) ? (_Float16)1.f : (_Float16)0.f;
 
     // ---- 1. forward recompute (h = tanh = 1 - 2r is what the backward needs: tanh' = 1 - h^2) ----
+    // MODE 3 rebuilds a state that it hands on as a result (omega_out): its activations are split round-to-nearest
+    // (the truncating split leaves a one-sided error of 2^-22 per operand, which the 2S rebuilds accumulate)
+    auto fsplit4 = [](f4 v, h4& hi, h4& lo) {
+        if (MODE == 3) split4r(v, hi, lo);
+        else split4(v, hi, lo);
+    };
+    auto fsplit2 = [](float v0, float v1) -> HiLo { return (MODE == 3) ? split2r(v0, v1) : split2v(v0, v1); };
     f4 r[L][2], h[L][2];
     h4 xs_hi[HT], xs_lo[HT];  // the split conditioner input, reused for its transposed form
     if constexpr (H == 32) {
         u4 a_, b_;
-        split2(x[0][0], x[0][1], a_[0], b_[0]);
-        split2(x[0][2], x[0][3], a_[1], b_[1]);
-        split2(x[1][0], x[1][1], a_[2], b_[2]);
-        split2(x[1][2], x[1][3], a_[3], b_[3]);
+        {
+            const HiLo hl_ = fsplit2(x[0][0], x[0][1]);
+            a_[0] = hl_.hi;
+            b_[0] = hl_.lo;
+        }
+        {
+            const HiLo hl_ = fsplit2(x[0][2], x[0][3]);
+            a_[1] = hl_.hi;
+            b_[1] = hl_.lo;
+        }
+        {
+            const HiLo hl_ = fsplit2(x[1][0], x[1][1]);
+            a_[2] = hl_.hi;
+            b_[2] = hl_.lo;
+        }
+        {
+            const HiLo hl_ = fsplit2(x[1][2], x[1][3]);
+            a_[3] = hl_.hi;
+            b_[3] = hl_.lo;
+        }
         const h8 xh = __builtin_bit_cast(h8, a_), xl = __builtin_bit_cast(h8, b_);
 #pragma unroll
         for (int mm = 0; mm < HT; ++mm) {
@@ -523,7 +548,7 @@ __device__ __forceinline__ void layer_bwd16(const float* img, ACCP& accp, float*
         }
     } else {
         h4 xh, xl;
-        split4(x[0], xh, xl);
+        fsplit4(x[0], xh, xl);
         xs_hi[0] = xh;
         xs_lo[0] = xl;
 #pragma unroll
@@ -538,7 +563,7 @@ __device__ __forceinline__ void layer_bwd16(const float* img, ACCP& accp, float*
 #pragma unroll
         for (int net = 0; net < 2; ++net) {
             h4 rh, rl, wh, wl;
-            split4(r[l][net], rh, rl);
+            fsplit4(r[l][net], rh, rl);
             hl(fg, FImg::g_wh(l, net), wh, wl);
             r[l + 1][net] = sig2_4(mm3(wh, wl, rh, rl, bias(FImg::b_bh(l, net))));
         }
@@ -555,8 +580,8 @@ __device__ __forceinline__ void layer_bwd16(const float* img, ACCP& accp, float*
     f4 dout[2][HT];
     {
         h4 rh[2], rl[2];
-        split4(r[L - 1][0], rh[0], rl[0]);
-        split4(r[L - 1][1], rh[1], rl[1]);
+        fsplit4(r[L - 1][0], rh[0], rl[0]);
+        fsplit4(r[L - 1][1], rh[1], rl[1]);
 #pragma unroll
         for (int mo = 0; mo < HT; ++mo) {
             h4 wh, wl;
@@ -583,6 +608,13 @@ __device__ __forceinline__ void layer_bwd16(const float* img, ACCP& accp, float*
                     dout[0][mo][j] = g;
                     dout[1][mo][j] = __builtin_fmaf(g * y[mo][j], e, gl);
                     gy[mo][j] = dy;
+                } else if (MODE == 3) {
+                    const float em = __builtin_amdgcn_exp2f(-sv[j]);
+                    const float g = gy[mo][j], d = y[mo][j] - tt[j];
+                    dout[0][mo][j] = g;
+                    dout[1][mo][j] = __builtin_fmaf(g, d, gl);
+                    y[mo][j] = d * em;
+                    gy[mo][j] = g * e;
                 } else {
                     const float em = __builtin_amdgcn_exp2f(-sv[j]);
                     const float g = gy[mo][j], yo = y[mo][j];
@@ -593,6 +625,9 @@ __device__ __forceinline__ void layer_bwd16(const float* img, ACCP& accp, float*
                     gy[mo][j] = dy;
                 }
             }
+            // the rebuilt input and its gradient are used by the NEXT step only: computed here, not sunk there with their
+            // four operands per element kept alive through the rest of the layer (no instruction is emitted)
+            if (MODE == 3) asm volatile("" : "+v"(y[mo]), "+v"(gy[mo]));
         }
     }
 
@@ -941,6 +976,193 @@ flow_bwd_f16_kernel(FlowBwdArgs a) {
     // ---- flush ----
     // a term above the fixed-point budget may have wrapped an accumulator: flag it (the reduction then poisons the
     // result instead of returning a wrong gradient; the budget is 2^13 per term in units where max |g_log_prob| is 1..2)
+    rev_flush<H, L, NW>(
+        a, m, mp, iters, fa.amax, glp_acc, isc, accb, scr, lane, wave,
+        [](float amax, float nadds) { return !(amax * nadds < 2147483648.f); },  // (also true for NaN / inf terms)
+        [&](const int* acc, int k) { return acc[acc_src<H, L, SPARE>(k, U)]; });
+}
+
+// ---------------------------------------------------------------------------
+// The sampling direction: backward of loss = f(z, sum_log_det) with (z, sum_log_det) = the frozen-statistics sampling
+// pass of the flow (include/tnf_sampletrain.h), in ONE kernel.  The sibling of flow_bwd_f16_kernel: same geometry, image
+// ring, accumulators and flush; it starts from the sampling OUTPUT z with g = d loss / d z and gamma = d loss /
+// d sum_log_det and walks the layers last to first.  In the sampling direction the streamed fold constants of layer c
+// stand BEHIND it, y = (x - B)/A, so each step first puts the fold back, x = A v + B, g <- g/A, and then runs the layer
+// as layer_bwd16 MODE 3.  On layers with an Affine the fold's gradients dA = -sum g_y y / A, dB = -sum g_y / A are kept
+// as the sums GA = sum g_y y, GB = sum g_y BEFORE the division: the accumulators are fixed point on the scale of the
+// cotangents, and flow_sample_fold_backward_kernel needs A dA and A dB only -- a sum of g_y / A would lose bits with
+// 1/A and get the loss multiplied by A again (measured: 1.6e-3 of the largest entry at A ~ 90, 1e-6 this way).
+// The state the walk ends on is the base draw omega.
+// ---------------------------------------------------------------------------
+struct FlowSampleBwdArgs {
+    FlowBwdArgs b;        // z0: the sampling output z; g_lp: gamma (M, N) or NULL; g_z: omega_out (M, N, D) or NULL;
+                          // gmax: bits of max(|g_zout|, |gamma|); glp_sum / glp_part collect sum gamma; g_fold holds
+                          // (GA | GB) per odd layer; the rest as there
+    const float* g_zout;  // (M, N, D) or NULL
+};
+
+// Put the fold behind a layer back on one half (features f0 + 16 mm + 4q + j): v <- A v + B, g <- g/A; with AFFINE the
+// tile's contributions to GA = sum g v, GB = sum g (both of the fold's OUTPUT side) go to gf, transposed and added as in
+// unfold_half.
+template <int H, bool AFFINE>
+__device__ __forceinline__ void refold_half(const float* fc, int* gf, FxAcc& fa, float* scrA, float* scrB, int lane,
+                                            int f0, f4 (&v)[(H + 15) / 16], f4 (&g)[(H + 15) / 16]) {
+    constexpr int D = 2 * H;
+    constexpr int HT = (H + 15) / 16;
+    const int s = lane & 15, q = lane >> 4;
+#pragma unroll
+    for (int mm = 0; mm < HT; ++mm) {
+        const int f = f0 + 16 * mm + 4 * q;
+        const f4 A = *reinterpret_cast<const f4*>(fc + f);
+        const f4 B = *reinterpret_cast<const f4*>(fc + D + f);
+        const f4 iA = *reinterpret_cast<const f4*>(fc + 2 * D + f);
+        f4 gx, gv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            gx[j] = g[mm][j] * iA[j];
+            gv[j] = g[mm][j] * v[mm][j];
+        }
+        if (AFFINE) {
+            const f4 ta = transpose16(gv, scrA, lane), tb = transpose16(g[mm], scrB, lane);
+            const float da = ((ta[0] + ta[1]) + (ta[2] + ta[3])) * fa.fx, db = ((tb[0] + tb[1]) + (tb[2] + tb[3])) * fa.fx;
+            fa.amax = amax3(fa.amax, da, db);
+            atomicAdd(gf + f0 + 16 * mm + s, fx_cvt(da));       // feature = row s of the transposed tile
+            atomicAdd(gf + D + f0 + 16 * mm + s, fx_cvt(db));
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            g[mm][j] = gx[j];
+            v[mm][j] = __builtin_fmaf(v[mm][j], A[j], B[j]);
+        }
+    }
+}
+
+// The walk's state is complete here: without this the compiler sinks the fold's multiplies towards their uses deep inside
+// the layer and keeps the fold constants (48 VGPRs at H = 32) alive next to the layer's own peak -- spills at H = 32,
+// one wave per SIMD less at H = 16.  No instruction is emitted.
+template <int HT>
+__device__ __forceinline__ void pin_state(f4 (&a)[HT], f4 (&b)[HT], f4 (&c)[HT], f4 (&d)[HT]) {
+#pragma unroll
+    for (int mm = 0; mm < HT; ++mm) asm volatile("" : "+v"(a[mm]), "+v"(b[mm]), "+v"(c[mm]), "+v"(d[mm]));
+}
+
+template <int H, int L, int NW, bool SPARE>
+__global__ void __launch_bounds__(NW * 64)
+flow_sample_bwd_kernel(FlowSampleBwdArgs sa) {
+    const FlowBwdArgs& a = sa.b;
+    typedef RevImage<H, L> R;
+    constexpr int D = 2 * H;
+    constexpr int HT = (H + 15) / 16;
+    constexpr int RU4 = R::FLOATS / 4;
+    constexpr int SLOT = (R::FLOATS + 255) & ~255;  // ring slot: whole 1-KB LDS-DMA pieces
+    constexpr int NPIECE = SLOT / 256;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int nl = 2 * a.S;
+    const int U = a.U;
+    typedef AccLayout<H, L> A_;
+    constexpr int ACC = A_::INTS;
+    float* ring = lds;                          // [2][SLOT]
+    int* accb = reinterpret_cast<int*>(lds + 2 * SLOT);  // [nl][ACC] fixed point
+    float* scr = lds + 2 * SLOT + nl * ACC;              // [NW][kRevNScr][kScr]
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: tile numbers, the scratch base and the
+    const int s = lane & 15, q = lane >> 4;                              // fetch loop stay in scalar registers
+    const int64_t m = grid_m();
+    if (m >= a.M) return;
+    const int64_t mp = a.Mp == 1 ? 0 : m;
+    float* scrA = scr + wave * kRevNScr * kScr;
+    float* scrB = scrA + (kRevNScr - 1) * kScr;
+    const u4* isrc = reinterpret_cast<const u4*>(a.rimg + mp * (int64_t)nl * R::FLOATS);
+
+    auto fetch = [&](int c, float* slot) { rev_fetch<RU4, NPIECE, NW>(isrc, c, slot, wave, lane); };
+    fetch(nl - 1, ring);
+    for (int i = threadIdx.x; i < nl * ACC; i += NW * 64) accb[i] = 0;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const auto [sc, isc] = pow2_scale(__uint_as_float(*a.gmax));  // the larger cotangent into [1, 2)
+    __syncthreads();
+
+    const int64_t ntiles = (a.N + 15) >> 4;
+    const int64_t stride = (int64_t)gridDim.x * NW;
+    const int64_t iters = (ntiles + stride - 1) / stride;
+    const float* zb = a.z0 + m * a.N * D;
+    const float* gzb = sa.g_zout ? sa.g_zout + m * a.N * D : nullptr;
+    const float* glb = a.g_lp ? a.g_lp + m * a.N : nullptr;
+    float* ob = a.g_z ? a.g_z + m * a.N * D : nullptr;
+    float glp_acc = 0.f;
+    FxAcc fa{a.fx, 0.f};
+    int step = 0;
+    const int64_t nsteps = iters * nl;
+
+    for (int64_t it = 0; it < iters; ++it) {
+        const int64_t tile = (it * gridDim.x + blockIdx.x) * NW + wave;
+        const int64_t row = tile * 16 + s;
+        const bool row_ok = row < a.N;
+        const int64_t rowc = row_ok ? row : a.N - 1;
+        f4 lo[HT], hi[HT], glo[HT], ghi[HT];
+        const float gl = (glb && row_ok) ? sc * glb[rowc] : 0.f;  // d loss / d (sum of s): a padded row adds nothing
+        if (q == 0) glp_acc += gl;  // the constant log-det of an Affine is +a per sample
+        {
+            int qo = 4 * q;  // opaque: no per-lane pointers zb + 4 q, gzb + 4 q kept in VGPR pairs across the walk
+            asm volatile("" : "+v"(qo));
+            const float* zr = zb + (rowc * D + qo);
+            const float gsc = row_ok ? sc : 0.f;  // a padded row repeats the last one: its gradient is zero
+#pragma unroll
+            for (int mm = 0; mm < HT; ++mm) {
+                lo[mm] = *reinterpret_cast<const f4*>(zr + 16 * mm);
+                hi[mm] = *reinterpret_cast<const f4*>(zr + H + 16 * mm);
+                glo[mm] = ghi[mm] = f4{0.f, 0.f, 0.f, 0.f};
+            }
+            if (gzb) {
+                const float* gr = gzb + (rowc * D + qo);
+#pragma unroll
+                for (int mm = 0; mm < HT; ++mm) {
+                    glo[mm] = gsc * *reinterpret_cast<const f4*>(gr + 16 * mm);
+                    ghi[mm] = gsc * *reinterpret_cast<const f4*>(gr + H + 16 * mm);
+                }
+            }
+        }
+
+        for (int c = nl - 1; c >= 0; --c, ++step) {
+            const float* img = ring + (step & 1) * SLOT;
+            const bool more = (int64_t)step + 1 < nsteps;
+            if (more) fetch((c == 0) ? nl - 1 : c - 1, ring + ((step + 1) & 1) * SLOT);
+            int* acc = accb + c * ACC;
+            const float* fc = img + R::C_OFF;
+            if ((c & 1) == 0) {  // RealNVP(upper) | BatchNorm
+                LdsFxAccum<H, L> ap{acc, fa, s, q};
+                refold_half<H, false>(fc, acc + A_::o_fold, fa, scrA, scrB, lane, 0, lo, glo);
+                refold_half<H, false>(fc, acc + A_::o_fold, fa, scrA, scrB, lane, H, hi, ghi);
+                pin_state<HT>(lo, hi, glo, ghi);
+                layer_bwd16<H, L, SPARE, 3>(img, ap, scrA, scrB, lane, U, lo, hi, glo, ghi, gl);
+            } else {             // RealNVP(lower) | BatchNorm | Affine
+                LdsFxAccum<H, L> ap{acc, fa, s, q};
+                refold_half<H, true>(fc, acc + A_::o_fold, fa, scrA, scrB, lane, 0, lo, glo);
+                refold_half<H, true>(fc, acc + A_::o_fold, fa, scrA, scrB, lane, H, hi, ghi);
+                pin_state<HT>(lo, hi, glo, ghi);
+                layer_bwd16<H, L, SPARE, 3>(img, ap, scrA, scrB, lane, U, hi, lo, ghi, glo, gl);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of the next image have landed
+            __syncthreads();
+        }
+        if (ob) {  // the base draw the walk ends on.  Its row is worked out again from the (scalar) tile number, made
+                   // opaque so that it is not the value above kept in VGPR pairs across the whole walk
+            int64_t t2 = (it * gridDim.x + blockIdx.x) * NW + wave;
+            int qo = 4 * q;  // (likewise: not a per-lane pointer ob + 4 q hoisted out of the tile loop)
+            asm volatile("" : "+s"(t2), "+v"(qo));
+            const int64_t row2 = t2 * 16 + s;
+            float* orow = ob + (row2 * D + qo);
+            if (row2 < a.N) {
+#pragma unroll
+                for (int mm = 0; mm < HT; ++mm) {
+                    *reinterpret_cast<f4*>(orow + 16 * mm) = lo[mm];
+                    *reinterpret_cast<f4*>(orow + H + 16 * mm) = hi[mm];
+                }
+            }
+        }
+    }
+
+    // ---- flush: as in flow_bwd_f16_kernel (same budget, same flag) ----
     rev_flush<H, L, NW>(
         a, m, mp, iters, fa.amax, glp_acc, isc, accb, scr, lane, wave,
         [](float amax, float nadds) { return !(amax * nadds < 2147483648.f); },  // (also true for NaN / inf terms)
@@ -1335,6 +1557,101 @@ int launch_flow_bwd_rev(const float* z0, const float* params, const float* bn_me
     return dispatch_hl(D, L, [&](auto h, auto l) {
         return launch_rev<h(), l()>(z0, params, bn_mean, bn_alpha, g_lp, g_z, g_params, M, Mp, N, S, U, pstride, gpstride, ws,
                                     overflow_out, st);
+    });
+}
+
+// ---- the sampling direction (flow_sample_bwd_kernel): the workspace is the one of launch_rev ----
+// The twin of flow_fold_backward_kernel (coupling_mfma.hip) for the sampling direction: from the sums over the samples
+// GA = sum g_y y, GB = sum g_y on the output side of the Affine y = e^a x + shift (bijectors.py:277-318, log_det = sum a)
+// and the summed log-det cotangent to the block's [alpha | shift] gradient:
+//   g_a = sum g_y (y - shift) + sum gamma = GA - shift GB + sum gamma,   g_shift = GB
+// (with the fold constants A = alpha_bn / e^a, B = mean_bn - shift A: -A dA + shift A dB and -A dB for dA = -GA / A,
+// dB = -GB / A).  g_fold: (Mp, 2S, 2, D), odd layers.  One workgroup per parameter row, one add per slot.  stage,
+// affine_off: the row's stage length and the Affine block's offset in a stage (FlowLayout, worked out by the launcher).
+__global__ void __launch_bounds__(256)
+flow_sample_fold_backward_kernel(const float* __restrict__ params, const float* __restrict__ g_fold,
+                                 const float* __restrict__ gsum, float* __restrict__ g_params, int D, int S, int64_t stage,
+                                 int64_t affine_off, int64_t pstride, int64_t gpstride) {
+    const int64_t mp = blockIdx.x;
+    const float sum_gamma = gsum[mp];
+    const float* p = params + mp * pstride;
+    float* gp = g_params + mp * gpstride;
+    for (int idx = threadIdx.x; idx < S * D; idx += 256) {
+        const int st = idx / D, d = idx - st * D;
+        const int64_t off = st * stage + affine_off;
+        const float* gf = g_fold + ((mp * 2 * S + 2 * st + 1) * 2) * D;
+        const float GA = gf[d], GB = gf[D + d];
+        gp[off + d] += __builtin_fmaf(-p[off + D + d], GB, GA) + sum_gamma;
+        gp[off + D + d] += GB;
+    }
+}
+
+template <int H, int L>
+static int launch_sample_rev(const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
+                             const float* g_zout, const float* g_sld, float* g_params, float* omega_out, int64_t M,
+                             int64_t Mp, int64_t N, int S, int U, int64_t pstride, int64_t gpstride, void* ws,
+                             int* overflow_out, hipStream_t st) {
+    constexpr int D = 2 * H;
+    typedef RevImage<H, L> R;
+    if (rev_image_floats(D, L) != R::FLOATS) return fail(TNF_ELAUNCH, "flow_sample_bwd: image size mismatch");
+    if (rev_lds_bytes(D, S, L, U) != (2 * (int64_t)PairLds<H, L>::SLOT + 2 * S * (int64_t)AccLayout<H, L>::INTS + (int64_t)kRevNW * kRevNScr * kScr) * 4)
+        return fail(TNF_ELAUNCH, "flow_sample_bwd: LDS size mismatch");
+    const RevWs w = rev_ws(M, Mp, N, D, S, L, U, ws);
+    if (hipMemsetAsync(w.gfold, 0, (size_t)w.zeroed_bytes, st) != hipSuccess)
+        return fail(TNF_ELAUNCH, "flow_sample_bwd: memset failed");
+    hipLaunchKernelGGL((flow_rev_images_kernel<H, L>), grid_xm(2 * S, Mp), dim3(64), 0, st, params, bn_mean, bn_alpha,
+                       w.rimg, S, U, pstride, Mp, 1.f);
+    // the pre-scale takes the larger of the two cotangents; an absent one is zero
+    if (g_zout)
+        if (int rc = launch_gmax(g_zout, M * N * D, w.gmax, st)) return rc;
+    if (g_sld)
+        if (int rc = launch_gmax(g_sld, M * N, w.gmax, st)) return rc;
+    const FlowLayout fl = flow_layout(D, S, L, U);
+    const int64_t bx = rev_blocks_x(M, N, false);
+    const int64_t units = (N + 15) / 16;
+    const int64_t adds = ((units + bx * kRevNW - 1) / (bx * kRevNW)) * kRevNW;  // the budget of launch_rev: 2^13 per term
+    int fbits = 31 - 13;
+    for (int64_t v = 1; v < adds; v <<= 1) --fbits;
+    if (fbits < 0) fbits = 0;
+    const float fx = ldexpf(1.f, fbits);
+    FlowSampleBwdArgs a{{z, g_sld, w.rimg, w.gmax, omega_out, g_params, w.gfold, w.glp_sum, M, Mp, N, gpstride, fl.stage,
+                         fl.p_up, S, U, fx, w.part, w.glpp, w.overflow},
+                        g_zout};
+    const int64_t nred = (Mp == 1 ? M : 1) * bx;
+    int rc = dispatch_bool(U <= 15, [&](auto spare) {
+        return launch_lds("flow_sample_bwd", flow_sample_bwd_kernel<H, L, kRevNW, spare()>, grid_xm(bx, M), dim3(kRevNW * 64),
+                          (size_t)rev_lds_bytes(D, S, L, U), st, a);
+    });
+    if (rc) return rc;
+    rc = check_launch("flow_sample_bwd");
+    if (rc) return rc;
+    const int P = 2 * (H * U + U) + (L - 1) * 2 * (U * U + U) + 2 * (U * H + H);
+    const int64_t prow = (int64_t)2 * S * (P + 2 * D);
+    hipLaunchKernelGGL(flow_bwd_reduce_kernel, grid_xm((prow + 255) / 256, Mp), dim3(256), 0, st, w.part, w.glpp, w.gmax,
+                       w.overflow, g_params, w.gfold, w.glp_sum, nred, 2 * S, P, D, gpstride, fl.stage, fl.p_up, fx, Mp, 0, U, L);
+    rc = check_launch("flow_bwd_reduce");
+    if (rc) return rc;
+    if (overflow_out && hipMemcpyAsync(overflow_out, w.overflow, sizeof(int), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return fail(TNF_ELAUNCH, "flow_sample_bwd: copy of the overflow flag failed");
+    hipLaunchKernelGGL(flow_sample_fold_backward_kernel, dim3((unsigned)Mp), dim3(256), 0, st, params, w.gfold, w.glp_sum,
+                       g_params, D, S, fl.stage, fl.p_up + fl.p_low, pstride, gpstride);
+    return check_launch("flow_sample_fold_backward");
+}
+
+int launch_flow_sample_bwd(const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
+                           const float* g_zout, const float* g_sld, float* g_params, float* omega_out, int64_t M,
+                           int64_t Mp, int64_t N, int D, int S, int L, int U, int64_t pstride, int64_t gpstride, void* ws,
+                           int* overflow_out, hipStream_t st) {
+    if (!flow_train_rev_supported(D, S, L, U))
+        return fail(TNF_EUNSUPPORTED, "flow_sample_bwd: D=%d S=%d L=%d U=%d", D, S, L, U);
+    if (N <= 0) return TNF_OK;
+    if (Mp == 1 && M > 1) {  // the rows of z, g_zout, g_sld and omega_out are contiguous: one batch of M * N
+        N *= M;
+        M = 1;
+    }
+    return dispatch_hl(D, L, [&](auto h, auto l) {
+        return launch_sample_rev<h(), l()>(z, params, bn_mean, bn_alpha, g_zout, g_sld, g_params, omega_out, M, Mp, N, S, U,
+                                           pstride, gpstride, ws, overflow_out, st);
     });
 }
 

@@ -266,6 +266,12 @@ int64_t flow_train_rev_workspace(int64_t M, int64_t Mp, int64_t N, int D, int S,
 int launch_flow_bwd_rev(const float* z0, const float* params, const float* bn_mean, const float* bn_alpha,
                         const float* g_lp, float* g_z, float* g_params, int64_t M, int64_t Mp, int64_t N, int D, int S,
                         int L, int U, int64_t pstride, int64_t gpstride, void* ws, int* overflow_out, hipStream_t st);
+// the same walk for the sampling direction (frozen statistics): from the output z with the cotangents g_zout (M, N, D)
+// and g_sld (M, N), either NULL = zero; omega_out optional; shapes and workspace of launch_flow_bwd_rev
+int launch_flow_sample_bwd(const float* z, const float* params, const float* bn_mean, const float* bn_alpha,
+                           const float* g_zout, const float* g_sld, float* g_params, float* omega_out, int64_t M,
+                           int64_t Mp, int64_t N, int D, int S, int L, int U, int64_t pstride, int64_t gpstride, void* ws,
+                           int* overflow_out, hipStream_t st);
 
 int launch_affine(int dtype, const void* z, const void* params, void* z_out, void* log_det,
                   int64_t Mz, int64_t Mp, int64_t N, int D, int inverse, int64_t pstride,

@@ -49,6 +49,11 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          when z does not require grad), 1 <= N <= 31, fusion AUTO or
                                          FLOW, ctx_train_supported (asked after the training pairs
                                          above: only calls that would otherwise compose bijectors)
+  train_sample      forward (frozen)     sample_training (default off), coupling, float32, grad      sampletrain_ops.flow_
+                                         mode on and params requires grad, const stats, 3-d, one     sample_train
+                                         parameter row or 32 samples per row, fusion AUTO or FLOW,
+                                         flow_sample_train_supported (asked after padded and fused,
+                                         which take the calls without a gradient)
   context_rows      forward (frozen),    context_rows (default off), coupling, plain, const stats,   ctxflow_ops.ctx_flow_
                     log_prob, inverse    3-d, several parameter rows = the larger batch, M_z = 1 or  forward_raw, ctx_flow_
                                          M (forward: M), 1 <= N <= 31, fusion AUTO or FLOW,          log_prob_raw
@@ -61,18 +66,19 @@ only the per-bijector composition differentiates through them); "not few" = not 
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
 a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `train_context`,
-`context_rows`, the batch-statistics chains (padded or not) and the per-layer chain do not.
+`context_rows`, `train_sample`, the batch-statistics chains (padded or not) and the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
-Sampling: the base density is evaluated first (base_log_density_f64), except that `padded` and the whole-flow `fused`
-kernel write log_q themselves for a float32 tensor draw (`Route.writes_log_q`).
+Sampling: the base density is evaluated first (base_log_density_f64), except that `padded`, the whole-flow `fused`
+kernel and `train_sample` (whose forward is one of those two) write log_q themselves for a float32 tensor draw
+(`Route.writes_log_q`).
 """
 import collections
 
 import numpy as np
 import torch
 
-from . import _lib, ctxflow_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops
+from . import _lib, ctxflow_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops, sampletrain_ops
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -162,6 +168,8 @@ class NormFlow(DensityEstimator):
     num_stages = _Checked("num_stages", int, _stages)
     num_layers = _Checked("num_layers", int, _layers)
     num_units = _Checked("num_units", int, _units)
+    # frozen-statistics sampling under autograd through one backward kernel (family `train_sample`); off: today's route
+    sample_training = False
 
     def __init__(self, D, conditioner=False, arch_type="AR", num_stages=1, num_layers=2,
                  num_units=15, support_layer=None, device=None):
@@ -336,6 +344,17 @@ class NormFlow(DensityEstimator):
         return (M > 1 and (z.size(0) == M or (z.size(0) == 1 and not z.requires_grad))
                 and ctxtrain_ops.ctx_train_supported(*shape, z.size(1)))
 
+    def _sample_train_ok(self, z, params, facts):
+        """One launch forward, one walk kernel backward for frozen-statistics sampling under autograd
+        (csrc/flow_bwd_f16.hip, flow_sample_bwd_kernel): only with the switch `sample_training` on, a coupling stack,
+        float32, grad mode on and params requiring grad, constant statistics, a 3-d draw, the fusion setting AUTO or
+        FLOW as for the `padded` family, and one parameter row or at least 32 samples per row."""
+        arch, shape, stats_graph, f32, _, _ = facts
+        return (getattr(self, "sample_training", False) and arch == "coupling" and f32 and torch.is_grad_enabled()
+                and params.requires_grad and not stats_graph and z.dim() == 3
+                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
+                and sampletrain_ops.flow_sample_train_supported(z.size(0), params.size(0), z.size(1), *shape))
+
     def _stats_in_graph(self):
         """Do the cached BatchNorm statistics still carry the graph of the batch-mode forward that produced them
         (per-bijector forward under autograd -- the reference's behaviour, bijectors.py:414-415)?  Then every later
@@ -417,6 +436,8 @@ class NormFlow(DensityEstimator):
                 return Route("train_" + pair, False, False)
         if op == "log_prob" and self._context_train_ok(z, params, f):
             return Route("train_context", False, False)
+        if op == "forward" and self._sample_train_ok(z, params, f):
+            return Route("train_sample", False, f32_draw)
         if self._context_rows_ok(op, z, params, f):  # asked last: nothing another family takes changes hands
             return Route("context_rows", False, False)
         return _BIJECTORS
@@ -492,6 +513,9 @@ class NormFlow(DensityEstimator):
                                                                want_log_q=route.writes_log_q)
             elif family == "context_rows":  # one wave per context; the support layer as for `padded`
                 z, sld = ctxflow_ops.ctx_flow_forward_raw(z, p_dev, *self._flow_args())
+            elif family == "train_sample":  # one autograd node, one backward kernel; the support layer as for `padded`
+                z, sld, *written = sampletrain_ops.flow_sample_train(z, p_dev, *self._flow_args(), self.fusion,
+                                                                     want_log_q=route.writes_log_q)
             elif family == "fused":  # `written` stays None where the selected kernel variant has no log_q output
                 z, sld, *written = ops.flow_forward_raw(z, p_dev, *self._flow_args(), self.fusion, interval_consts=consts,
                                                         want_log_q=route.writes_log_q)
