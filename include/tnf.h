@@ -250,7 +250,8 @@ int tnf_maf(int32_t dtype, const void* z, const void* params, const void* masks,
             int32_t inverse, int64_t params_row_stride, void* stream);
 /* MAF.inverse_and_log_det (bijectors.py:758-764) with the per-dimension f_alpha(z) (M,N,D) as an extra output.
  * The backward of the sampling direction (autograd through MAF.forward_and_log_det, bijectors.py:752-754) is built on
- * it: x solves G(x, theta) = omega with G the inverse map, whose Jacobian is triangular with diagonal e^-alpha. */
+ * it: x solves G(x, theta) = omega with G the inverse map, whose Jacobian is triangular with diagonal e^-alpha.
+ * The same backward in one float32 kernel, without this call: tnf_maf_sample_bwd_f32 (tnf_arsample.h). */
 int tnf_maf_inverse_alpha(int32_t dtype, const void* z, const void* params, const void* masks, void* z_out, void* log_det,
                           void* alpha_out, int64_t M_z, int64_t M_p, int64_t N, int32_t D, int32_t num_layers,
                           int32_t num_units, int64_t params_row_stride, void* stream);
@@ -639,4 +640,5 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
 #include "tnf_ctxflow.h"  /* per-context flows with fewer than 32 samples each, one launch per call: the same */
 #include "tnf_ctxtrain.h" /* ... and their log_prob backward, one launch per call: the same */
 #include "tnf_sampletrain.h" /* training through frozen-statistics sampling in one backward kernel: the same */
+#include "tnf_arsample.h"    /* ... and for the autoregressive flow (MAF sampling backward in one kernel): the same */
 #endif /* TNF_H */

@@ -269,6 +269,18 @@ SAMPLETRAIN_SIGNATURES = {
                                                _i32, _i64, _i64, _vp, _i64, _vp, _vp]),
 }
 
+# training an autoregressive flow through its samples: the MAF sampling backward in one kernel, alone and with the
+# frozen-statistics stack folded in, declared in include/tnf_arsample.h: an eleventh table (tests/test_arsample_host.py)
+ARSAMPLE_SIGNATURES = {
+    "tnf_maf_sample_bwd_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "tnf_arsample_launch_count": (_i64, []),
+    "tnf_maf_sample_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64,
+                                              _i64, _vp]),
+    "tnf_ar_flow_sample_bwd_workspace_bytes": (_i64, [_i64, _i32]),
+    "tnf_ar_flow_sample_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32,
+                                                  _i64, _i64, _vp, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -279,7 +291,7 @@ def _load():
         )
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
-                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES):
+                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES, ARSAMPLE_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

@@ -286,6 +286,9 @@ class MAF(Bijector):
     num_layers = _Checked("num_layers", int, _clamp_maf_layers)
     num_units = _Checked("num_units", int, _clamp_maf_units)
     fwd_fac = _Checked("fwd_fac", bool)
+    # autograd through forward_and_log_det (sampling) in ONE backward kernel where it applies (float32, D <= 32,
+    # fwd_fac masks, exact-f32 operands: ops._MafFn, include/tnf_arsample.h); off: the D + 2 launches of before
+    fused_sampling_backward = False
 
     def __init__(self, D, num_layers, num_units, fwd_fac=True):
         super().__init__(D)
@@ -340,7 +343,8 @@ class MAF(Bijector):
         return cache[key]
 
     def forward_and_log_det(self, z, params):
-        return ops.maf(z, params, self._masks_for(z.dtype), self.D, self.num_layers, self.num_units, False)
+        return ops.maf(z, params, self._masks_for(z.dtype), self.D, self.num_layers, self.num_units, False,
+                       bool(self.fused_sampling_backward) and self.fwd_fac)
 
     def inverse_and_log_det(self, z, params):
         return ops.maf(z, params, self._masks_for(z.dtype), self.D, self.num_layers, self.num_units, True)

@@ -14,86 +14,10 @@
 // A workgroup owns one parameter row (context) and walks its tiles grid-stride; the accumulators leave
 // LDS once, masked, by plain stores (per-context rows, one workgroup per row) or one atomic per
 // parameter per workgroup.
-#include "mfma_tile.h"
+#include "maf_bwd_tile.h"
 #include "support_math.h"
-#include "launch.h"
 
 namespace tnf {
-
-struct MafBLayout {  // group numbering shared by the folded image, the transposed image and the accumulators
-    int UT, DT, L;
-    __host__ __device__ int n0() const { return 2 * UT * DT; }
-    __host__ __device__ int nh() const { return 2 * UT * UT; }
-    __host__ __device__ int NWG() const { return n0() + (L - 1) * nh() + n0(); }
-    __host__ __device__ int NBG() const { return (L - 1) * 2 * UT + 2 * DT; }
-    // (net, out tile, in tile) of each layer
-    __host__ __device__ int g0(int net, int ut, int mm) const { return (net * UT + ut) * DT + mm; }
-    __host__ __device__ int gh(int l, int net, int uo, int ui) const { return n0() + l * nh() + (net * UT + uo) * UT + ui; }
-    __host__ __device__ int g2(int net, int mo, int ui) const { return n0() + (L - 1) * nh() + (net * DT + mo) * UT + ui; }
-    __host__ __device__ int bh(int l, int net, int uo) const { return l * 2 * UT + net * UT + uo; }
-    __host__ __device__ int b2(int net, int mo) const { return (L - 1) * 2 * UT + net * DT + mo; }
-    __host__ __device__ int fwd_floats() const { return NWG() * 256 + NBG() * 16; }
-};
-
-// folded forward image (same maths as build_maf_image of maf_mfma.hip) and the plain transposed image:
-// group (net, out tile, in tile), lane (r, q): W*M [in = 16 it + r][out = 16 ot + 4q + j].
-// The (layer, net, out tile) units are dealt round-robin to the workgroup's `nwaves` waves: with one
-// workgroup per context the build is on the critical path of every context.
-__device__ void build_maf_bwd_images(float* fimg, float* timg, const float* __restrict__ p0, const float* __restrict__ mk0,
-                                     MafBLayout wl, int D, int U, int lane, int wave, int nwaves, int bf) {
-    const int r = lane & 15, q = lane >> 4;
-    float* fw = fimg + lane * 4;
-    float* fb = fimg + wl.NWG() * 256 + q * 4;
-    float* tw = timg + lane * 4;
-    const bool bias_lane = r == 0;
-    int unit = 0;
-    const float* p = p0;
-    const float* mk = mk0;
-    for (int layer = 0; layer <= wl.L; ++layer) {
-        const int din = layer == 0 ? D : U, dout = layer == wl.L ? D : U;
-        const int IT = layer == 0 ? wl.DT : wl.UT, OT = layer == wl.L ? wl.DT : wl.UT;
-        const float* w[2] = {p, p + din * dout};
-        for (int net = 0; net < 2; ++net) {
-            // scale of the folded weights: layer 0 feeds a tanh (c = 2 log2 e); later layers consume
-            // r = (1 - tanh)/2 (factor -2) and feed a tanh (c) or the outputs (1 for mu, log2 e for alpha)
-            const float outsc = layer == wl.L ? (net == 0 ? 1.f : kLog2e) : kTwoLog2e;
-            const float wsc = layer == 0 ? outsc : -2.f * outsc;
-            for (int ot = 0; ot < OT; ++ot, ++unit) {
-                if (unit % nwaves != wave) continue;
-                const int g_base = layer == 0 ? wl.g0(net, ot, 0) : (layer == wl.L ? wl.g2(net, ot, 0) : wl.gh(layer - 1, net, ot, 0));
-                float csum = 0.f;
-                for (int it = 0; it < IT; ++it) {
-                    f4 vf, vt;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        // folded: row = output unit 16 ot + r, K = input 16 it + 4q + j
-                        const int o = 16 * ot + r, k = 16 * it + 4 * q + j;
-                        const bool ok = k < din && o < dout;
-                        const float raw = ld_sel(w[net], k * dout + o, ok) * ld_sel(mk, k * dout + o, ok);
-                        csum += raw;
-                        vf[j] = wsc * raw;
-                        // transposed: row = input 16 it + r, K = output 16 ot + 4q + j
-                        const int k2 = 16 * it + r, o2 = 16 * ot + 4 * q + j;
-                        const bool ok2 = k2 < din && o2 < dout;
-                        vt[j] = ld_sel(w[net], k2 * dout + o2, ok2) * ld_sel(mk, k2 * dout + o2, ok2);
-                    }
-                    *reinterpret_cast<f4*>(fw + (g_base + it) * 256) = rbf16_4(vf, bf);
-                    *reinterpret_cast<f4*>(tw + (g_base + it) * 256) = rbf16_4(vt, bf);
-                }
-                if (layer > 0) {  // accumulator initial values: column sums (there are no biases in MAF)
-                    csum = reduce_q(csum);
-                    f4 bv;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) bv[j] = outsc * __shfl(csum, 4 * q + j);
-                    const int bg = layer == wl.L ? wl.b2(net, ot) : wl.bh(layer - 1, net, ot);
-                    if (bias_lane) *reinterpret_cast<f4*>(fb + bg * 16) = bv;
-                }
-            }
-        }
-        p += 2 * din * dout;
-        mk += din * dout;
-    }
-}
 
 struct MafBwdArgs {
     const float* z;
@@ -122,8 +46,6 @@ struct MafBwdArgs {
     float fx;
     int bf16;  // != 0: the bf16 experiment (every MFMA operand rounded to bf16, mfma_tile.h rbf16)
 };
-
-constexpr int kMafLMax = 3;
 
 template <int DT, int UT, bool VEC>
 __global__ void __launch_bounds__(256)
@@ -511,24 +433,10 @@ maf_bwd_mfma_kernel(MafBwdArgs a, MafBLayout wl) {
     }
 }
 
-static MafBLayout maf_blayout(int D, int L, int U) {
-    MafBLayout wl;
-    wl.UT = (U + 15) / 16;
-    wl.DT = (D + 15) / 16;
-    wl.L = L;
-    return wl;
-}
-
-static size_t maf_bwd_smem(const MafBLayout& wl, int nacc = 1) {
-    return (size_t)(wl.fwd_floats() + (1 + nacc) * wl.NWG() * 256 + 4 * 2 * 272 + 11 * 16 * wl.DT + 4) * sizeof(float);
-}
-
 bool maf_bwd_mfma_supported(int D, int L, int U) {
     if (D < 1 || D > 32 || L < 1 || L > kMafLMax || U < 1 || U > 64) return false;
     return maf_bwd_smem(maf_blayout(D, L, U)) <= 156 * 1024;
 }
-
-static int maf_bwd_nacc(int D, int L, int U) { return maf_bwd_smem(maf_blayout(D, L, U), 4) <= 156 * 1024 ? 4 : 1; }
 
 __global__ void __launch_bounds__(256)
 maf_gmax_kernel(const float* __restrict__ g, int64_t n, unsigned* __restrict__ out) {
@@ -551,11 +459,7 @@ static int launch_maf_bwd_args(MafBwdArgs& a, hipStream_t st) {
     const size_t smem = maf_bwd_smem(wl, nacc);
     a.nacc = nacc;
     a.bf16 = g_operand_prec == 1;
-    const int64_t ntiles = (a.N + 15) / 16;
-    int64_t bx = (ntiles + 3) / 4;
-    if (a.Mp > 1) bx = 1;  // one workgroup owns the context's gradient row: plain stores
-    else if (bx > 512) bx = 512;
-    const dim3 grid = grid_xm(bx, a.M);
+    const dim3 grid = maf_bwd_grid(a.M, a.Mp, a.N);
     auto go = [&](auto dt) {  // D <= 32: one or two feature tiles
         return dispatch_1to4(wl.UT, [&](auto ut) {
             return dispatch_bool((a.D % 4) == 0, [&](auto vec) {
@@ -625,9 +529,7 @@ int launch_ar_flow_backward(const float* z, const float* params, const float* ma
         if (blocks > 256) blocks = 256;
         hipLaunchKernelGGL(maf_gmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g_lp, n, gmax);
         const int64_t ntiles = (N + 15) / 16;
-        int64_t bx = (ntiles + 3) / 4;
-        if (Mp > 1) bx = 1;
-        else if (bx > 512) bx = 512;
+        const int64_t bx = maf_bwd_grid(M, Mp, N).x;
         const int64_t adds = (ntiles + bx - 1) / bx;  // tiles (= terms per accumulator) per workgroup
         int fbits = 31 - 13;
         for (int64_t v = 1; v < adds; v <<= 1) --fbits;

@@ -30,6 +30,12 @@ only the per-bijector composition differentiates through them); "not few" = not 
   ar_train          log_prob             AR, fused_ar_training, grad mode on, const stats, float32,  ar_flow_log_prob_train
                                          params requires grad and z does not, 3-d, M_z >= M_p,
                                          ar_flow_supported, ar_flow_train_supported
+  ar_train_sample   forward (frozen)     ar_sample_training (default off), AR, float32, grad mode    arsample_ops.ar_flow_
+                                         on and params requires grad, const stats, 3-d, M_p = 1 or   sample_train
+                                         M_z, any support layer (run behind it as its own op),
+                                         ar_flow_supported, maf_sample_bwd_supported, operand
+                                         precision 0 (asked after ar_fused, which takes the calls
+                                         without a gradient)
   padded            forward (frozen),    coupling, plain, const stats, not few, 3-d, fusion AUTO or  flow_padded_forward_raw,
                     log_prob, inverse    FLOW, flow_padded_supported                                 flow_padded_log_prob_raw
   fused             forward (frozen),    coupling, plain, const stats, not few, has_fast_path        flow_forward_raw,
@@ -66,7 +72,8 @@ only the per-bijector composition differentiates through them); "not few" = not 
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
 a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `train_context`,
-`context_rows`, `train_sample`, the batch-statistics chains (padded or not) and the per-layer chain do not.
+`context_rows`, `train_sample`, `ar_train_sample`, the batch-statistics chains (padded or not) and the per-layer chain do
+not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
 Sampling: the base density is evaluated first (base_log_density_f64), except that `padded`, the whole-flow `fused`
@@ -78,7 +85,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, ctxflow_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops, sampletrain_ops
+from . import _lib, arsample_ops, ctxflow_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops, sampletrain_ops
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -170,6 +177,9 @@ class NormFlow(DensityEstimator):
     num_units = _Checked("num_units", int, _units)
     # frozen-statistics sampling under autograd through one backward kernel (family `train_sample`); off: today's route
     sample_training = False
+    # the same for arch_type "AR" (family `ar_train_sample`); with fresh statistics the per-bijector composition runs
+    # with the MAF's one-kernel sampling backward (MAF.fused_sampling_backward) for the call; off: today's routes
+    ar_sample_training = False
 
     def __init__(self, D, conditioner=False, arch_type="AR", num_stages=1, num_layers=2,
                  num_units=15, support_layer=None, device=None):
@@ -272,6 +282,17 @@ class NormFlow(DensityEstimator):
                 and not stats_graph and params.requires_grad and not z.requires_grad and z.dim() == 3 and f32
                 and z.size(0) == max(z.size(0), params.size(0))
                 and ops.ar_flow_supported(D, L, U) and ops.ar_flow_train_supported(z.size(0), params.size(0), D, L, U))
+
+    def _ar_sample_train_ok(self, z, params, facts=None):
+        """One kernel forward, one fused kernel backward for frozen-statistics sampling of the AR stack under autograd
+        (csrc/maf_sample_bwd.hip): only with the switch `ar_sample_training` on, float32, grad mode on and params
+        requiring grad, constant statistics, a 3-d draw, one parameter row or one per block of samples, exact-f32
+        operands, and a shape both kernels cover."""
+        arch, (D, _, L, U), stats_graph, f32, _, _ = facts or self._facts(z, params)
+        return (getattr(self, "ar_sample_training", False) and arch == "AR" and f32 and torch.is_grad_enabled()
+                and params.requires_grad and not stats_graph and z.dim() == 3
+                and ops.current_operand_precision() == "fp32"
+                and arsample_ops.ar_flow_sample_train_supported(z.size(0), params.size(0), D, L, U))
 
     def _ar_args(self):
         maf, bn = self.bijectors[0], self.bijectors[1]
@@ -403,12 +424,15 @@ class NormFlow(DensityEstimator):
         if arch == "affine" or (op == "inverse" and sup is not None):
             return _BIJECTORS
         if arch == "AR":
-            if op == "forward" and not (freeze_bn and (interval or sup is None)):
+            if op == "forward" and not freeze_bn:
                 return _BIJECTORS
-            if self._ar_fused_ok(z, params, f):
-                return Route("ar_fused", interval, False)
-            if op == "log_prob" and self._ar_train_ok(z, params, f):
-                return Route("ar_train", interval, False)
+            if op != "forward" or interval or sup is None:  # (sampling fuses a ToInterval layer or none)
+                if self._ar_fused_ok(z, params, f):
+                    return Route("ar_fused", interval, False)
+                if op == "log_prob" and self._ar_train_ok(z, params, f):
+                    return Route("ar_train", interval, False)
+            if op == "forward" and self._ar_sample_train_ok(z, params, f):
+                return Route("ar_train_sample", False, False)
             return _BIJECTORS
         # `fused` is asked through the instance: tests switch this family (never `padded`) off with an attribute of it
         forced = vars(self).get("_fused_ok")
@@ -495,19 +519,32 @@ class NormFlow(DensityEstimator):
         for b in self._bn_layers():
             b.stats_reduce = None if freeze_bn else self.batch_stats_reduce
         if family == "bijectors":
-            idx = 0
-            for bijector in self.bijectors[:self._n_core]:
-                if bijector.name == "BatchNorm":
-                    z, log_det = bijector(z, use_last=freeze_bn)
-                else:
-                    n = bijector.count_num_params()
-                    z, log_det = bijector(z, p_dev[:, idx:idx + n])
-                    idx += n
-                log_q = log_q - log_det
+            # fresh statistics on an AR stack with `ar_sample_training`: the MAF's sampling backward is one kernel for the
+            # duration of this call (the decision is recorded on the autograd node, so a later backward keeps it)
+            maf = self.bijectors[0] if (self.arch_type == "AR" and getattr(self, "ar_sample_training", False)
+                                        and not freeze_bn) else None
+            restore = None if maf is None else maf.fused_sampling_backward
+            if maf is not None:
+                maf.fused_sampling_backward = True
+            try:
+                idx = 0
+                for bijector in self.bijectors[:self._n_core]:
+                    if bijector.name == "BatchNorm":
+                        z, log_det = bijector(z, use_last=freeze_bn)
+                    else:
+                        n = bijector.count_num_params()
+                        z, log_det = bijector(z, p_dev[:, idx:idx + n])
+                        idx += n
+                    log_q = log_q - log_det
+            finally:
+                if maf is not None:
+                    maf.fused_sampling_backward = restore
         else:
             written = None
             if family == "ar_fused":
                 z, sld = ops.ar_flow_forward_raw(z, p_dev, *self._ar_args(), interval_consts=consts)
+            elif family == "ar_train_sample":  # one autograd node, one backward kernel; any support layer runs below
+                z, sld = arsample_ops.ar_flow_sample_train(z, p_dev, *self._ar_args())
             elif family == "padded":  # no fused support layer: it runs below as its own kernel
                 z, sld, *written = ops.flow_padded_forward_raw(z, p_dev, *self._flow_args(),
                                                                want_log_q=route.writes_log_q)

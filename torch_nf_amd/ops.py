@@ -855,11 +855,20 @@ class _MafFn(torch.autograd.Function):
     with diagonal e^-alpha.  With K(g_out, g_ld) the inverse-direction backward kernel (K_z = G_x^T g_out + A_x^T g_ld,
     K_theta likewise; A = sum alpha), the total gradient w.r.t. x is w = g_x + A_x^T g_ld, v = G_x^-T w is reached
     exactly by D sweeps of  v <- v + e^alpha (g_x - K_z(v, -g_ld))  (the error moves strictly along the
-    autoregressive order), and then  g_omega = v,  g_theta = -K_theta(v, -g_ld)."""
+    autoregressive order), and then  g_omega = v,  g_theta = -K_theta(v, -g_ld).
+    `fused_bwd` (MAF.fused_sampling_backward, default off): where arsample_ops.maf_sample_route_ok holds, that whole
+    backward is ONE kernel (tnf_maf_sample_bwd_f32: the nets evaluated once, D - 1 delta-only sweeps in registers, one
+    pass with the weight gradients); elsewhere it changes nothing."""
 
     @_records_options
-    def forward(ctx, z, params, masks, D, L, U, inverse):
+    def forward(ctx, z, params, masks, D, L, U, inverse, fused_bwd=False):
         z_out, log_det = maf_raw(z, params, masks, D, L, U, inverse)
+        ctx.fused_bwd = False
+        if fused_bwd and not inverse:
+            from . import arsample_ops
+
+            # M_z = M: a shared draw under per-context rows needs g_omega summed over the contexts (the route below)
+            ctx.fused_bwd = z.shape[0] == z_out.shape[0] and arsample_ops.maf_sample_route_ok(z_out, params, D, L, U)
         if inverse:
             ctx.save_for_backward(z, params, masks)
         else:
@@ -881,7 +890,16 @@ class _MafFn(torch.autograd.Function):
         D, L, U, inverse, Mz = ctx.cfg
         if inverse:
             gz, gp = grad.maf_backward(z, params, masks, g_z, g_ld, D, L, U)
-            return gz, gp, None, None, None, None, None
+            return gz, gp, None, None, None, None, None, None
+        if ctx.fused_bwd:
+            from . import arsample_ops
+
+            none = (None,) * 6
+            if g_z is None and g_ld is None:
+                return (None, None) + none
+            g_omega, gp = arsample_ops.maf_sample_bwd_raw(z, params, masks, g_z, g_ld, D, L, U,
+                                                          want_omega=ctx.needs_input_grad[0])
+            return (g_omega, gp) + none
         x = z.detach()
         dev = _lib.require_device()
         gx = torch.zeros_like(x) if g_z is None else g_z.to(x.dtype)
@@ -895,12 +913,12 @@ class _MafFn(torch.autograd.Function):
         g_omega = v
         if Mz != v.shape[0]:
             g_omega = v.sum(0, keepdim=True)
-        return g_omega, -gp, None, None, None, None, None
+        return g_omega, -gp, None, None, None, None, None, None
 
 
-def maf(z, params, masks, D, L, U, inverse):
+def maf(z, params, masks, D, L, U, inverse, fused_sampling_backward=False):
     if torch.is_grad_enabled() and (z.requires_grad or params.requires_grad):
-        return _MafFn.apply(z, params, masks, D, L, U, inverse)
+        return _MafFn.apply(z, params, masks, D, L, U, inverse, fused_sampling_backward)
     return maf_raw(z, params, masks, D, L, U, inverse)
 
 
