@@ -85,7 +85,7 @@ int tnf_get_option(int32_t key, int32_t* value);
  * that select a kernel through an option or a shape read the counters around a call to prove the intended kernel ran (a
  * backward runs on autograd's thread, where a thread-local option set elsewhere would be silently absent; a forward call
  * may move to another kernel where the first one's operands no longer fit the LDS).  Families 0-6: backward kernels.
- * Families 7-15: forward kernels, one count per launch of the kernel named; the small preparation launches of the
+ * Families 7-18: forward kernels, one count per launch of the kernel named; the small preparation launches of the
  * flow_range2 chains (operand images, fold constants) and of cond_flow (operand image) are not counted. */
 enum {
     TNF_DIAG_BWD_LAYER_FP32 = 0,  /* coupling_bwd_mfma_kernel: fp32-MFMA layer backward */
@@ -107,7 +107,9 @@ enum {
     TNF_DIAG_COND_FLOW = 15,      /* cond_flow_kernel: conditional flow log_prob, training forward and sampling */
     TNF_DIAG_FLOW_PADDED = 16,    /* flow_fused2_kernel in its padded layouts (tnf_flow_padded_log_prob_f32) */
     TNF_DIAG_FLOW_PADDED_FWD = 17, /* the same, sampling direction (tnf_flow_padded_forward_f32) */
-    TNF_DIAG_FAMILIES = 18
+    TNF_DIAG_COUPLING_WIDE = 18,  /* coupling_wide_kernel: the wide fp32-MFMA layer kernel (bijector-level calls and the
+                                   * wide per-layer chains of both directions), one count per launch */
+    TNF_DIAG_FAMILIES = 19
 };
 int64_t tnf_diag_launch_count(int32_t family);
 

@@ -51,7 +51,7 @@ def test_header_exports_and_bindings_in_step():
         assert "TNF_CTXFLOW_COUNT_%s = %d" % (n, i) in header
     assert "TNF_CTXFLOW_COUNTERS = 2" in header
     assert (ctxflow_ops.COUNT_LOG_PROB, ctxflow_ops.COUNT_FORWARD) == (0, 1)
-    assert _lib.DIAG_FAMILIES == 18  # a counter space of its own: the flow families are a closed set
+    assert _lib.DIAG_FAMILIES == 19  # a counter space of its own: the flow families are a closed set
     for which in range(2):
         assert lib.tnf_ctx_flow_launch_count(which) >= 0
     assert lib.tnf_ctx_flow_launch_count(2) == -1 and b"tnf_ctx_flow_launch_count" in lib.tnf_last_error()

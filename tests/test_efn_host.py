@@ -52,7 +52,7 @@ def test_header_exports_and_bindings_in_step():
     assert "TNF_EFN_COUNTERS = 3" in header
     assert "#define TNF_EFN_MAX_D %d" % _lib.EFN_MAX_D in header and _lib.EFN_MAX_D == 64
     assert "#define TNF_EFN_MAX_DF %d" % _lib.EFN_MAX_DF in header and _lib.EFN_MAX_DF == 1024
-    assert _lib.DIAG_FAMILIES == 18  # a counter space of its own: the flow families are a closed set
+    assert _lib.DIAG_FAMILIES == 19  # a counter space of its own: the flow families are a closed set
 
 
 def test_queries_host_side():

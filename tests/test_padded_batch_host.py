@@ -54,7 +54,7 @@ def test_header_exports_and_bindings_in_step():
     for i, n in enumerate(COUNTERS):
         assert "TNF_PADBATCH_COUNT_%s = %d" % (n, i) in header
     assert "TNF_PADBATCH_COUNTERS = 5" in header
-    assert _lib.DIAG_FAMILIES == 18  # a counter space of its own: the flow families are a closed set
+    assert _lib.DIAG_FAMILIES == 19  # a counter space of its own: the flow families are a closed set
     for which in range(5):
         assert lib.tnf_padbatch_launch_count(which) >= 0
     assert lib.tnf_padbatch_launch_count(5) == -1 and b"tnf_padbatch_launch_count" in lib.tnf_last_error()

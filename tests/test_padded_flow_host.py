@@ -156,7 +156,7 @@ def test_declared_in_header_and_bound():
     for n in ("tnf_flow_padded_supported", "tnf_flow_padded_workspace_bytes", "tnf_flow_padded_log_prob_f32",
               "tnf_flow_padded_forward_f32"):
         assert hasattr(raw, n) and n in L_.SIGNATURES
-    assert (L_.DIAG_FLOW_PADDED, L_.DIAG_FLOW_PADDED_FWD, L_.DIAG_FAMILIES) == (16, 17, 18)
+    assert (L_.DIAG_FLOW_PADDED, L_.DIAG_FLOW_PADDED_FWD, L_.DIAG_FAMILIES) == (16, 17, 19)
 
 
 def test_routing_predicate_host_side():

@@ -55,7 +55,7 @@ def test_header_exports_and_bindings_in_step():
     for n in ("EMBED_ROWS", "GATHER_ROWS", "EMBED_PARAMS", "GATHER_PARAMS", "BWD"):
         assert "TNF_PADTRAIN_COUNT_%s = %d" % (n, getattr(_lib, "PADTRAIN_COUNT_" + n)) in header
     assert "TNF_PADTRAIN_COUNTERS = 5" in header
-    assert _lib.DIAG_FAMILIES == 18  # a counter space of its own: the flow families are a closed set
+    assert _lib.DIAG_FAMILIES == 19  # a counter space of its own: the flow families are a closed set
     for which in range(5):
         assert lib.tnf_padtrain_launch_count(which) >= 0
     assert lib.tnf_padtrain_launch_count(5) == -1 and b"tnf_padtrain_launch_count" in lib.tnf_last_error()

@@ -25,8 +25,8 @@ DIAG_BWD_LAYER_FP32, DIAG_BWD_LAYER_F16, DIAG_BWD_GENERIC, DIAG_BWD_FLOW_REV = 0
 DIAG_MAF_BWD_MFMA, DIAG_MAF_BWD_GENERIC, DIAG_BWD_WIDE = 4, 5, 6
 DIAG_FLOW_FUSED2, DIAG_FLOW_FUSED2_FWD, DIAG_FLOW_FUSED3, DIAG_FLOW_F16, DIAG_FLOW_FP32 = 7, 8, 9, 10, 11
 DIAG_FLOW_RANGE2, DIAG_FLOW_RANGE2_FWD, DIAG_COUPLING_MFMA, DIAG_COND_FLOW = 12, 13, 14, 15
-DIAG_FLOW_PADDED, DIAG_FLOW_PADDED_FWD = 16, 17
-DIAG_FAMILIES = 18
+DIAG_FLOW_PADDED, DIAG_FLOW_PADDED_FWD, DIAG_COUPLING_WIDE = 16, 17, 18
+DIAG_FAMILIES = 19
 EF_MVN, EF_DIRICHLET = 0, 1
 EF_COUNT_DOT, EF_COUNT_DOT_BWD = 0, 1  # tnf_ef_launch_count
 MOG_COUNT_LOGPROB, MOG_COUNT_LOGPROB_BWD, MOG_COUNT_SAMPLE = 0, 1, 2  # tnf_mog_launch_count

@@ -235,6 +235,7 @@ int launch_coupling_wide(const MfmaLayerArgs& a, hipStream_t st) {
         return fail(TNF_EUNSUPPORTED, "coupling_wide: no kernel for D=%d L=%d U=%d", a.D, a.L, a.U);
     const int64_t M = a.Mz > a.Mp ? a.Mz : a.Mp;
     if (a.N <= 0) return TNF_OK;
+    diag_count(TNF_DIAG_COUPLING_WIDE);
     const WideLayout wl = wide_layout(a.D, a.L, a.U);
     const size_t smem = (size_t)(4 * 128 + wl.floats()) * sizeof(float);
     const int64_t ntiles = (a.N + 15) / 16;
