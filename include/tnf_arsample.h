@@ -20,10 +20,18 @@
  *   tnf_maf_num_params(D, L, U); masks as tnf_maf takes them; g_x (M, N, D) and g_ld (M, N), the cotangents of the sample
  *   and of the log-det -- either may be NULL (= zero), not both.
  *   -> g_omega (M, N, D), the gradient w.r.t. the base draw; NULL: not wanted.
- *   -> g_params (M_p, gpstride): ACCUMULATED (the caller zeroes it), as tnf_maf_backward does.
- *   M_p is 1 or M.  Per-context rows (M_p = M > 1) run one workgroup per context for any N >= 1 and write each gradient
- *   once, in a fixed order: bit-reproducible.  One shared row is walked by a persistent grid and flushed through atomics:
- *   not bit-reproducible from call to call.
+ *   -> g_params (M_p, gpstride): the caller zeroes it, in every case.  With one shared row (M_p = 1) everything is
+ *   ADDED to what is there (atomics).  With per-context rows (M_p = M > 1) the MAF block is WRITTEN (plain stores; what
+ *   was there is lost) and the Affine slice of the stack entry below is ADDED (its finalize kernel).
+ *   M_p is 1 or M.  Per-context rows run one workgroup per context for any N >= 1 and write each gradient once.  They
+ *   are bit-reproducible from call to call where four private accumulator copies fit the LDS (maf_bwd_nacc == 4: each
+ *   wave adds its tiles in a fixed order, the flush adds the four copies in wave order).  Where only one shared copy
+ *   fits, the four waves add into it with LDS float atomics, whose order is not fixed once N > 16 (a second wave has a
+ *   tile): not bit-reproducible.  One shared row is walked by a persistent grid and flushed through atomics: not
+ *   bit-reproducible from call to call either.
+ *   Alignment: every pointer is float-aligned.  The float4 loads and stores are taken only when D % 4 == 0 AND x, g_x (if
+ *   given) and g_omega (if given) are 16-byte aligned; otherwise the call runs the scalar-access instantiation -- the
+ *   same values, a slower load stage.  The same holds for z and g_z of the stack entry.
  * tnf_ar_flow_sample_bwd_workspace_bytes(M_p, D): the workspace of the call below (fold | fold sums).  TNF_EINVAL for
  *   M_p < 1 or D < 1.
  * tnf_ar_flow_sample_bwd_f32: the stack with frozen statistics, z = e^a (x - mean_bn) / alpha_bn + b,
@@ -31,7 +39,7 @@
  *   forward; params (M_p, pstride) = [MAF | a (D) | b (D)]; bn_mean / bn_alpha (D), constants; g_z (M, N, D) and g_sld
  *   (M, N), either may be NULL, not both.  The kernel rebuilds x = z A + B (A = alpha_bn e^-a, B = mean_bn - b A), forms
  *   g_x = g_z / A and reduces GZ = sum_n g_z z, GB = sum_n g_z, GS = sum_n g_sld per parameter row; a small finalize
- *   kernel adds g_a = GZ - b GB + GS and g_b = GB.  -> g_params (M_p, gpstride), accumulated as above.  The workspace
+ *   kernel adds g_a = GZ - b GB + GS and g_b = GB.  -> g_params (M_p, gpstride), zeroed by the caller, as above.  The workspace
  *   must be 16-byte aligned.
  * Refused before any launch: a NULL required pointer, both cotangents NULL, M < 1, M_p not in {1, M}, N < 0, pstride or
  * gpstride below the row length, g_params == params are TNF_EINVAL; an unsupported shape is TNF_EUNSUPPORTED; a NULL or

@@ -12,6 +12,7 @@ import torch
 
 from conftest import ROOT
 import arsample_restatement as R
+import maf_restatement as MR
 import test_route_table as RT
 
 import torch_nf_amd as tnf
@@ -65,6 +66,106 @@ def test_restatement_against_float64_autograd(oracle, D, L, U, Mp):
         ((z * g_x).sum() + (sld * g_ld).sum()).backward()
         got = R.ar_flow_sample_bwd(z.detach(), q.detach(), Ms, pr["mean"], pr["alpha"], g_x, g_ld, D, L, U)
         torch.testing.assert_close(got, q.grad, **TOL64)
+
+
+@pytest.mark.parametrize("Mp", [1, 2])
+@pytest.mark.parametrize("D,L,U", [(2, 1, 15), (5, 1, 20), (6, 2, 15), (8, 3, 16)])
+def test_folded_restatement_against_float64_autograd(oracle, D, L, U, Mp):
+    """folded=True -- r = 1 / (1 + 2^a), folded weights, column-sum seeds, alpha in log2 units, h = 1 - 2 r,
+    tanh' = 4 r (1 - r) -- is in float64 the same function: bijector and stack, both cotangents and each alone."""
+    M, N = 2, 7
+    pr = problem(oracle, D, L, U, M, Mp, N, seed=10 * D + Mp)
+    Ms, n = pr["Ms"], pr["n"]
+    for cz, cl in ((1.0, 1.0), (1.0, 0.0), (0.0, 1.0)):
+        g_x, g_ld = cz * pr["wz"], cl * pr["wl"]
+        p, om = pr["p"][:, :n].clone().requires_grad_(), pr["omega"].clone().requires_grad_()
+        x, ld = oracle.maf(om, p, D, L, U, Ms, False)
+        ((x * g_x).sum() + (ld * g_ld).sum()).backward()
+        g_om, g_p, trail = R.maf_sample_bwd(x.detach(), p.detach(), Ms, g_x, g_ld, D, L, U, folded=True)
+        assert len(trail) == D - 1 and g_om.dtype == g_p.dtype == torch.float64
+        torch.testing.assert_close(g_om, om.grad, **TOL64)
+        torch.testing.assert_close(g_p, p.grad, **TOL64)
+        q = pr["p"].clone().requires_grad_()
+        x, ld = oracle.maf(pr["omega"], q[:, :n], D, L, U, Ms, False)
+        y, ld2 = oracle.bn_forward_frozen(x, pr["mean"], pr["alpha"])
+        z, ld3 = oracle.affine(y, q[:, n:], D, False)
+        ((z * g_x).sum() + ((ld + ld2 + ld3) * g_ld).sum()).backward()
+        got = R.ar_flow_sample_bwd(z.detach(), q.detach(), Ms, pr["mean"], pr["alpha"], g_x, g_ld, D, L, U, folded=True)
+        torch.testing.assert_close(got, q.grad, **TOL64)
+    if Mp == 1:  # 16-row tiles added in tile order (the long-row variant): the same sums
+        om1, wz1, wl1 = (pr[k][:1].repeat(1, 5, *([1] * (pr[k].dim() - 2))) for k in ("omega", "wz", "wl"))
+        x = oracle.maf(om1, pr["p"][:, :n], D, L, U, Ms, False)[0]
+        whole = R.maf_sample_bwd(x, pr["p"][:, :n], Ms, wz1, wl1, D, L, U, folded=True)
+        tiled = R.maf_sample_bwd(x, pr["p"][:, :n], Ms, wz1, wl1, D, L, U, folded=True, tile=16)
+        assert tiled[0].shape == whole[0].shape and x.shape[1] == 35  # two full tiles and three rows
+        torch.testing.assert_close(tiled[0], whole[0], **TOL64)
+        torch.testing.assert_close(tiled[1], whole[1], **TOL64)
+
+
+# ---- the host half of tests/test_gpu_arsample_domain.py ------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sweep(oracle):
+    s = R.Sweep(tnf, oracle)
+    for section in R.SECTIONS:
+        s.need(section)
+    return s
+
+
+def test_sweep_grid_reaches_every_cell():
+    """The counts are asserted so that a later edit of MR's grids cannot empty a cell silently."""
+    domain = [(D, L, U) for D in range(2, 33) for L in (1, 2, 3) for U in range(5, 65)]
+    shapes, refused = R.maf_shapes(), R.refused_shapes()
+    assert len(MR.backward_cases()) == 48 and len(shapes) == 40 and len(refused) == 8
+    assert {R.cell(*s) for s in shapes} == {R.cell(*s) for s in domain if MR.bwd_supported(*s)} and len({R.cell(*s) for s in shapes}) == 40
+    assert sum(MR.nacc(*s) == 1 for s in shapes) == 12
+    for s in MR.backward_cases():  # the refused shapes are exactly the library's
+        assert (lib.tnf_maf_sample_bwd_supported(*s) == 0) == (s in refused), s
+    # what tests/test_gpu_arsample.py's seven shapes never reach
+    cells = {R.cell(*s) for s in shapes}
+    assert {c for c in cells if c[1] == 4} and {c for c in cells if c[:2] == (1, 3)} and {c for c in cells if c[:2] == (2, 2)}
+    assert {c for c in cells if c[0] == 2 and not c[2] and c[1] <= 2} and {c for c in cells if c[3] == 3 and c[1] > 1}
+    assert any(s[0] == 17 for s in shapes)
+    flow = R.flow_shapes()
+    assert len(MR.train_cases()) == 24 and len(flow) == 20
+    assert all(lib.tnf_maf_sample_bwd_supported(*s) == 1 and lib.tnf_ar_flow_supported(*s) == 1 for s in flow)
+    assert {MR.tiles(s[0], s[2]) for s in R.nf_shapes()} == {MR.tiles(s[0], s[2]) for s in flow} and len(R.nf_shapes()) == 8
+    assert [(MR.nacc(*s), R.vec(s[0])) for s in R.ARG_CELLS] == [(4, True), (4, False), (1, True), (1, False)]
+    assert all(s in shapes for s in R.ARG_CELLS) and R.ALIGN_CELL[0] == 16 and MR.nacc(*R.ALIGN_CELL) == 4
+    assert [MR.nacc(*s) for s in MR.LONG_CELLS] == [1, 4] and all(MR.bwd_supported(*s) for s in MR.LONG_CELLS)
+    assert MR.bwd_bx(MR.LONG_N, 1) == 512 and MR.tiles_per_wave(MR.LONG_N, 512) == 2
+    assert MR.bwd_supported(*MR.SMALL_WEIGHT[:3])
+    with pytest.raises(Exception):  # D = 1: supported by the predicate, but the package builds no masks for it
+        tnf.MAF(1, 1, 5)
+    assert lib.tnf_maf_sample_bwd_supported(1, 1, 5) == 1
+
+
+def test_sweep_noise_table(sweep):
+    """The float32 folded restatement against the float64 restatement per group (quantity, L) on the sweep's own inputs:
+    above rounding to nothing, and 4 x it within CAP for every group but the small-weight one."""
+    print("\n" + sweep.table())
+    assert (len(sweep.maf), len(sweep.args), len(sweep.flow), len(sweep.nf)) == (40 * 3, 4 * 6, 20 * 2, 8)
+    for (name, L), v in sorted(sweep.noise.items()):
+        assert 1e-9 < v and (name.startswith("small-weight") or sweep.bar(name, L) <= R.CAP), (name, L, v)
+
+
+def test_planted_defects_fail_the_bars(sweep):
+    """One sweep too few at D = 2, the - g_ld term dropped from d_alpha, GS left out of g_a: each in float64 on the
+    smallest cell where it shows, each at least 10 x outside its group's bar."""
+    s = (2, 1, 5)
+    c = sweep.maf[(s, MR.BWD_ROWS[0])]
+    args = (c.x.double(), c.params.double(), c.Ms, c.g_x.double(), c.g_ld.double(), *s)
+    for defect in (dict(sweeps=0), dict(drop_gld=True)):
+        got = R.maf_sample_bwd(*args, **defect)
+        ratios = [MR.gerr(got[i], c.f64[i]) / sweep.bar("maf " + part, 1) for i, part in enumerate(("g_omega", "g_params"))]
+        print("planted %s: %.1f, %.1f x the bar" % (defect, *ratios))
+        assert max(ratios) >= 10.0
+    s = R.flow_shapes()[0]
+    f = sweep.flow[(s, R.FLOW_ROWS[0])]
+    got = R.ar_flow_sample_bwd(f.z.double(), f.params.double(), f.Ms, *(t.double() for t in f.stat), f.g_z.double(),
+                               f.g_sld.double(), *s, drop_gs=True)
+    ratio = MR.gerr(f.split(got)[1], f.split(f.f64["both"])[1]) / sweep.bar("flow g_affine", s[1])
+    print("planted GS left out of g_a: %.1f x the bar" % ratio)
+    assert ratio >= 10.0 and MR.gerr(f.split(got)[0], f.split(f.f64["both"])[0]) == 0.0
 
 
 # ---- the C ABI, host side ------------------------------------------------------------------------------------------------

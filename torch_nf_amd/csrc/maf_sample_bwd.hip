@@ -387,6 +387,13 @@ ar_sample_fold_backward_kernel(const float* __restrict__ params, int64_t pstride
 
 static std::atomic<long long> g_arsample_launches;
 
+// The VEC instantiation moves x, g_x and g_omega as float4: D % 4 == 0 keeps every row a multiple of 16 bytes, so the
+// rows are aligned exactly when the bases are.  (The sibling launch_maf_bwd_args of maf_bwd_mfma.hip still picks VEC on
+// D % 4 == 0 alone and relies on 16-byte aligned tensors from its callers.)
+static bool maf_sample_bwd_vec(const MafSampleBwdArgs& a) {
+    return (a.D % 4) == 0 && is_aligned(a.x, 16) && (!a.g_x || is_aligned(a.g_x, 16)) && (!a.g_omega || is_aligned(a.g_omega, 16));
+}
+
 static int launch_maf_sample_bwd(MafSampleBwdArgs& a, hipStream_t st) {
     const MafBLayout wl = maf_blayout(a.D, a.L, a.U);
     a.nacc = maf_bwd_nacc(a.D, a.L, a.U);
@@ -394,7 +401,7 @@ static int launch_maf_sample_bwd(MafSampleBwdArgs& a, hipStream_t st) {
     const dim3 grid = maf_bwd_grid(a.M, a.Mp, a.N);
     auto go = [&](auto dt) {  // D <= 32: one or two feature tiles
         return dispatch_1to4(wl.UT, [&](auto ut) {
-            return dispatch_bool((a.D % 4) == 0, [&](auto vec) {
+            return dispatch_bool(maf_sample_bwd_vec(a), [&](auto vec) {
                 return launch_lds("maf_sample_bwd", maf_sample_bwd_kernel<dt(), ut(), vec()>, grid, dim3(256), smem, st, a, wl);
             });
         });
