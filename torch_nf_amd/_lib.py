@@ -281,6 +281,20 @@ ARSAMPLE_SIGNATURES = {
                                                   _i64, _i64, _vp, _i64, _vp]),
 }
 
+# sampling an autoregressive flow with fresh batch statistics, one call each way, declared in include/tnf_arbatch.h: a
+# twelfth table (tests/test_arbatch_host.py)
+ARBATCH_SIGNATURES = {
+    "tnf_ar_flow_batch_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "tnf_ar_flow_batch_train_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "tnf_arbatch_launch_count": (_i64, [_i32]),
+    "tnf_ar_flow_forward_batch_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32]),
+    "tnf_ar_flow_forward_batch_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32,
+                                                     _i64, _f32, _vp, _i64, _vp]),
+    "tnf_ar_flow_batch_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32]),
+    "tnf_ar_flow_batch_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32,
+                                                 _i64, _i64, _vp, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -291,7 +305,8 @@ def _load():
         )
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
-                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES, ARSAMPLE_SIGNATURES):
+                  PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES, ARSAMPLE_SIGNATURES,
+                  ARBATCH_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

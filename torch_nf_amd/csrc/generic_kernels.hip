@@ -401,6 +401,16 @@ int launch_bn_moments(const float* z, double* moments, int64_t rows, int D, hipS
     return check_launch("bn_moments");
 }
 
+// moments = [sum (D) | sum of squares (D)] of rows >= 1 rows, overwritten; the slot of the count is zeroed, not written
+int launch_bn_moment_sums(const float* z, double* moments, int64_t rows, int D, hipStream_t st) {
+    if (hipMemsetAsync(moments, 0, sizeof(double) * (2 * (size_t)D + 1), st) != hipSuccess)
+        return fail(TNF_ELAUNCH, "bn_moment_sums: memset failed");
+    int64_t blocks = (rows + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    (void)launch_bn_sums(z, moments, rows, D, blocks, (rows + blocks - 1) / blocks, st);
+    return check_launch("bn_moment_sums");
+}
+
 // mean / alpha / 1/alpha / log-det from moments (the count is read from moments[2 D])
 int launch_bn_finalize(const double* moments, float* mean_out, float* alpha_out, float* rstd, float* log_det, int D,
                        float eps, hipStream_t st) {

@@ -221,6 +221,8 @@ int launch_flow_fused_f16(const float* z, const float* images, const float* fold
                           const float* interval_consts = nullptr);  // fused ToInterval support layer (7, D)
 
 int launch_bn_moments(const float* z, double* moments, int64_t rows, int D, hipStream_t st);
+// the sums of launch_bn_moments alone, for a caller that knows the row count itself: one kernel on every path
+int launch_bn_moment_sums(const float* z, double* moments, int64_t rows, int D, hipStream_t st);
 int launch_bn_finalize(const double* moments, float* mean_out, float* alpha_out, float* rstd, float* log_det, int D,
                        float eps, hipStream_t st);
 int64_t flow_forward_batch_workspace(int64_t Mp, int D, int S, int L);
@@ -424,6 +426,11 @@ int launch_maf_mfma(const MafArgs& a, hipStream_t st);
 int launch_ar_fold(const float* params, int64_t pstride, int64_t p_maf, const float* bn_mean, const float* bn_alpha,
                    float* fold, float* ldc, int64_t Mp, int D, int inverse, hipStream_t st);
 bool maf_bwd_mfma_supported(int D, int L, int U);
+// maf_sample_bwd.hip, batch mode: the sampling backward walk on rows z with x = z A' + B', g_x = g_z C0 + C1 + z C2
+// formed in its load stage; coef (Mp, 5, D) = A' | B' | C0 | C1 | C2
+int launch_maf_sample_bwd_batch(const float* z, const float* params, const float* masks, const float* g_z,
+                                const float* g_sld, const float* coef, float* g_params, int64_t M, int64_t Mp, int64_t N,
+                                int D, int L, int U, int64_t pstride, int64_t gpstride, hipStream_t st);
 // workspace of the AR-flow entries: fold (Mp, 2, D) | ldc (Mp) and, for the backward, g_fold (Mp, 2, D) | glp_sum (Mp) |
 // max |g_log_prob| (1) -- those three zeroed as one block
 struct ArFlowWs {

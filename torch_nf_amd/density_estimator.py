@@ -36,6 +36,15 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          ar_flow_supported, maf_sample_bwd_supported, operand
                                          precision 0 (asked after ar_fused, which takes the calls
                                          without a gradient)
+  ar_batch_chain    forward, fresh       ar_batch_forward (default off), AR, plain, 3-d, one         arbatch_ops.ar_flow_
+                    statistics           parameter row per z row, M*N >= 2, batch_stats_reduce       forward_batch_raw
+                                         unset, M*N*D <= 160,000 (a tie above: DESIGN.md 22),
+                                         ar_flow_batch_supported; any support layer runs behind it
+                                         as its own op
+  ar_batch_train    forward, fresh       the same at any batch size with float32 in place of plain,  arbatch_ops.ar_flow_
+                    statistics           grad mode on and params requires grad, operand precision    forward_batch_train
+                                         0, ar_flow_batch_train_supported (D <= 32; one autograd
+                                         node)
   padded            forward (frozen),    coupling, plain, const stats, not few, 3-d, fusion AUTO or  flow_padded_forward_raw,
                     log_prob, inverse    FLOW, flow_padded_supported                                 flow_padded_log_prob_raw
   fused             forward (frozen),    coupling, plain, const stats, not few, has_fast_path        flow_forward_raw,
@@ -85,7 +94,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, arsample_ops, ctxflow_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops, sampletrain_ops
+from . import _lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops, sampletrain_ops
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -180,6 +189,9 @@ class NormFlow(DensityEstimator):
     # the same for arch_type "AR" (family `ar_train_sample`); with fresh statistics the per-bijector composition runs
     # with the MAF's one-kernel sampling backward (MAF.fused_sampling_backward) for the call; off: today's routes
     ar_sample_training = False
+    # fresh-statistics sampling of arch_type "AR" -- nf(N), cde(x, N) -- as one C call forward and one backward (families
+    # `ar_batch_chain` / `ar_batch_train`); off: today's per-bijector composition
+    ar_batch_forward = False
 
     def __init__(self, D, conditioner=False, arch_type="AR", num_stages=1, num_layers=2,
                  num_units=15, support_layer=None, device=None):
@@ -293,6 +305,27 @@ class NormFlow(DensityEstimator):
                 and params.requires_grad and not stats_graph and z.dim() == 3
                 and ops.current_operand_precision() == "fp32"
                 and arsample_ops.ar_flow_sample_train_supported(z.size(0), params.size(0), D, L, U))
+
+    def _ar_batch_family(self, z, params, facts):
+        """Fresh-statistics sampling of the AR stack as one C call each way (csrc/ar_flow_batch.hip): only with the switch
+        `ar_batch_forward` on, float32, a 3-d draw with one block per parameter row, at least two rows in the batch and no
+        sample-sharded statistics.  "ar_batch_chain": the call is plain and the forward kernel covers the shape;
+        "ar_batch_train": grad mode on, params requiring grad, exact-f32 operands and a shape the sampling backward
+        covers too (D <= 32); None: the per-bijector composition.  One measured exclusion (DESIGN.md 22,
+        profiles/r18_arbatchbench.txt): without autograd the chain saves launches only, a clear win up to 160,000 values
+        in the batch (1.15 .. 1.44 x at 100 x 25 .. 400 samples, D = 4, and 100 x 25 .. 100, D = 16) and a tie from 640,000
+        (1.00 .. 1.09 x, the rounds overlap in most runs), so `ar_batch_chain` is offered up to M N D = 160,000 only."""
+        _, (D, _, L, U), _, f32, plain, _ = facts
+        if not (getattr(self, "ar_batch_forward", False) and f32 and z.dim() == 3 and z.size(0) == params.size(0)
+                and z.size(0) * z.size(1) >= 2 and self.batch_stats_reduce is None):
+            return None
+        if plain:
+            small = z.size(0) * z.size(1) * D <= 160000
+            return "ar_batch_chain" if small and arbatch_ops.ar_flow_batch_supported(D, L, U) else None
+        if (torch.is_grad_enabled() and params.requires_grad and ops.current_operand_precision() == "fp32"
+                and arbatch_ops.ar_flow_batch_train_supported(D, L, U)):
+            return "ar_batch_train"
+        return None
 
     def _ar_args(self):
         maf, bn = self.bijectors[0], self.bijectors[1]
@@ -424,8 +457,9 @@ class NormFlow(DensityEstimator):
         if arch == "affine" or (op == "inverse" and sup is not None):
             return _BIJECTORS
         if arch == "AR":
-            if op == "forward" and not freeze_bn:
-                return _BIJECTORS
+            if op == "forward" and not freeze_bn:  # fresh batch statistics: one call each way behind `ar_batch_forward`
+                family = self._ar_batch_family(z, params, f)
+                return Route(family, False, False) if family else _BIJECTORS
             if op != "forward" or interval or sup is None:  # (sampling fuses a ToInterval layer or none)
                 if self._ar_fused_ok(z, params, f):
                     return Route("ar_fused", interval, False)
@@ -562,7 +596,13 @@ class NormFlow(DensityEstimator):
                 # statistics its own forward(use_last=False) would have cached
                 bns = self._bn_layers()
                 shape = (self.D, self.num_stages, self.num_layers, self.num_units, bns[0].eps)
-                if family == "batch_chain":
+                if family in ("ar_batch_chain", "ar_batch_train"):  # [MAF, BatchNorm, Affine]: one layer of statistics
+                    entry = (arbatch_ops.ar_flow_forward_batch_raw if family == "ar_batch_chain"
+                             else arbatch_ops.ar_flow_forward_batch_train)
+                    z, sld, mean, alpha = entry(z, p_dev, self.bijectors[0]._masks_for(torch.float32), self.D,
+                                                self.num_layers, self.num_units, bns[0].eps)
+                    means, alphas = [mean.detach()], [alpha.detach()]
+                elif family == "batch_chain":
                     z, sld, means, alphas = ops.flow_forward_batch_raw(z, p_dev, *shape,
                                                                        reduce_moments=self.batch_stats_reduce)
                 elif family == "batch_chain_padded":  # ... the same two at 2 <= D <= 63 but 32, at the embedded width
