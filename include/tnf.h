@@ -644,4 +644,5 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
 #include "tnf_sampletrain.h" /* training through frozen-statistics sampling in one backward kernel: the same */
 #include "tnf_arsample.h"    /* ... and for the autoregressive flow (MAF sampling backward in one kernel): the same */
 #include "tnf_arbatch.h"     /* the autoregressive flow sampled with fresh batch statistics, one call each way: the same */
+#include "tnf_ctxsample.h"   /* per-context flows with fewer than 32 samples each, trained through their samples: the same */
 #endif /* TNF_H */

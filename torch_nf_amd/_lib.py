@@ -295,6 +295,16 @@ ARBATCH_SIGNATURES = {
                                                  _i64, _i64, _vp, _i64, _vp]),
 }
 
+# training per-context flows with fewer than 32 samples each through their frozen-statistics samples: the backward of
+# tnf_ctx_flow_forward_f32 in one launch, declared in include/tnf_ctxsample.h: a thirteenth table
+# (tests/test_ctx_sample_host.py)
+CTXSAMPLE_SIGNATURES = {
+    "tnf_ctx_sample_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i64]),
+    "tnf_ctx_sample_launch_count": (_i64, []),
+    "tnf_ctx_sample_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
+                                              _i64, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -306,7 +316,7 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
                   PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES, ARSAMPLE_SIGNATURES,
-                  ARBATCH_SIGNATURES):
+                  ARBATCH_SIGNATURES, CTXSAMPLE_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

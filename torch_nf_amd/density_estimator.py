@@ -69,6 +69,13 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          parameter row or 32 samples per row, fusion AUTO or FLOW,
                                          flow_sample_train_supported (asked after padded and fused,
                                          which take the calls without a gradient)
+  train_context_    forward (frozen)     context_sample_training (default off), coupling, float32,   ctxsample_ops.ctx_flow_
+  sample                                 grad mode on and params requires grad, const stats, 3-d,    sample_train
+                                         several parameter rows, one block of draws per row,
+                                         1 <= N <= 31, fusion AUTO or FLOW, ctx_sample_supported
+                                         (asked after train_sample, which takes one parameter row
+                                         or 32 samples per row; independent of context_rows and
+                                         context_training)
   context_rows      forward (frozen),    context_rows (default off), coupling, plain, const stats,   ctxflow_ops.ctx_flow_
                     log_prob, inverse    3-d, several parameter rows = the larger batch, M_z = 1 or  forward_raw, ctx_flow_
                                          M (forward: M), 1 <= N <= 31, fusion AUTO or FLOW,          log_prob_raw
@@ -81,8 +88,8 @@ only the per-bijector composition differentiates through them); "not few" = not 
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
 a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `train_context`,
-`context_rows`, `train_sample`, `ar_train_sample`, the batch-statistics chains (padded or not) and the per-layer chain do
-not.
+`context_rows`, `train_sample`, `train_context_sample`, `ar_train_sample`, the batch-statistics chains (padded or not) and
+the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
 Sampling: the base density is evaluated first (base_log_density_f64), except that `padded`, the whole-flow `fused`
@@ -94,7 +101,8 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops, sampletrain_ops
+from . import (_lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxsample_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops,
+               sampletrain_ops)
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -192,6 +200,10 @@ class NormFlow(DensityEstimator):
     # fresh-statistics sampling of arch_type "AR" -- nf(N), cde(x, N) -- as one C call forward and one backward (families
     # `ar_batch_chain` / `ar_batch_train`); off: today's per-bijector composition
     ar_batch_forward = False
+    # frozen-statistics sampling under autograd with several parameter rows and fewer than 32 draws per row -- cde(x, N,
+    # freeze_bn=True) with a handful of draws per x -- through one backward launch (family `train_context_sample`); off:
+    # today's per-bijector composition
+    context_sample_training = False
 
     def __init__(self, D, conditioner=False, arch_type="AR", num_stages=1, num_layers=2,
                  num_units=15, support_layer=None, device=None):
@@ -409,6 +421,20 @@ class NormFlow(DensityEstimator):
                 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
                 and sampletrain_ops.flow_sample_train_supported(z.size(0), params.size(0), z.size(1), *shape))
 
+    def _context_sample_train_ok(self, z, params, facts):
+        """One launch each way for frozen-statistics sampling under autograd with several parameter rows and fewer than
+        32 draws per row (csrc/flow_ctx.hip forward, csrc/flow_ctx_sample_bwd.hip backward): only with the switch
+        `context_sample_training` on (independent of `context_rows` and `context_training`), a coupling stack, float32,
+        grad mode on and params requiring grad, constant statistics, a 3-d draw with one block per parameter row, and the
+        fusion setting AUTO or FLOW as for the `padded` family."""
+        arch, shape, stats_graph, f32, _, _ = facts
+        if not (getattr(self, "context_sample_training", False) and arch == "coupling" and f32 and torch.is_grad_enabled()
+                and params.requires_grad and not stats_graph and z.dim() == 3
+                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
+            return False
+        M = params.size(0)
+        return M > 1 and z.size(0) == M and ctxsample_ops.ctx_sample_supported(*shape, z.size(1))
+
     def _stats_in_graph(self):
         """Do the cached BatchNorm statistics still carry the graph of the batch-mode forward that produced them
         (per-bijector forward under autograd -- the reference's behaviour, bijectors.py:414-415)?  Then every later
@@ -496,6 +522,8 @@ class NormFlow(DensityEstimator):
             return Route("train_context", False, False)
         if op == "forward" and self._sample_train_ok(z, params, f):
             return Route("train_sample", False, f32_draw)
+        if op == "forward" and self._context_sample_train_ok(z, params, f):
+            return Route("train_context_sample", False, False)
         if self._context_rows_ok(op, z, params, f):  # asked last: nothing another family takes changes hands
             return Route("context_rows", False, False)
         return _BIJECTORS
@@ -584,6 +612,8 @@ class NormFlow(DensityEstimator):
                                                                want_log_q=route.writes_log_q)
             elif family == "context_rows":  # one wave per context; the support layer as for `padded`
                 z, sld = ctxflow_ops.ctx_flow_forward_raw(z, p_dev, *self._flow_args())
+            elif family == "train_context_sample":  # one autograd node, one launch each way; the support layer as above
+                z, sld = ctxsample_ops.ctx_flow_sample_train(z, p_dev, *self._flow_args())
             elif family == "train_sample":  # one autograd node, one backward kernel; the support layer as for `padded`
                 z, sld, *written = sampletrain_ops.flow_sample_train(z, p_dev, *self._flow_args(), self.fusion,
                                                                      want_log_q=route.writes_log_q)
