@@ -305,6 +305,17 @@ CTXSAMPLE_SIGNATURES = {
                                               _i64, _i64, _vp]),
 }
 
+# the whole coupling flow in one launch at 17 <= num_units <= 64 and any 2 <= D <= 64, declared in
+# include/tnf_wideflow.h: a fourteenth table (tests/test_wideflow_host.py)
+WIDEFLOW_SIGNATURES = {
+    "tnf_wide_flow_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "tnf_wide_flow_launch_count": (_i64, [_i32]),
+    "tnf_wide_flow_log_prob_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                                  _i64, _vp]),
+    "tnf_wide_flow_forward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                                 _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -316,7 +327,7 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
                   PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES, ARSAMPLE_SIGNATURES,
-                  ARBATCH_SIGNATURES, CTXSAMPLE_SIGNATURES):
+                  ARBATCH_SIGNATURES, CTXSAMPLE_SIGNATURES, WIDEFLOW_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

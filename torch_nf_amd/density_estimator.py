@@ -47,6 +47,14 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          node)
   padded            forward (frozen),    coupling, plain, const stats, not few, 3-d, fusion AUTO or  flow_padded_forward_raw,
                     log_prob, inverse    FLOW, flow_padded_supported                                 flow_padded_log_prob_raw
+  wide_flow         forward (frozen),    wide_flow (default off), coupling, plain, const stats, not  wideflow_ops.wide_flow_
+                    log_prob, inverse    few, 3-d, fusion AUTO or FLOW, wide_flow_supported (17 <=   forward_raw, wide_flow_
+                                         num_units <= 64, any 2 <= D <= 64, the 2 S operand images   log_prob_raw
+                                         within the LDS budget), and not (forward with several
+                                         parameter rows at D % 8 == 0, D < 32: the wide chain is
+                                         faster there) (asked before fused: with the
+                                         switch on it takes the D % 8 == 0 shapes from the wide
+                                         per-layer chain)
   fused             forward (frozen),    coupling, plain, const stats, not few, has_fast_path        flow_forward_raw,
                     log_prob, inverse    (`_fused_ok`; whole flow or per-layer chain as `fusion`     flow_log_prob_raw
                                          resolves)
@@ -88,7 +96,7 @@ only the per-bijector composition differentiates through them); "not few" = not 
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
 a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `train_context`,
-`context_rows`, `train_sample`, `train_context_sample`, `ar_train_sample`, the batch-statistics chains (padded or not) and
+`context_rows`, `wide_flow`, `train_sample`, `train_context_sample`, `ar_train_sample`, the batch-statistics chains (padded or not) and
 the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
@@ -102,7 +110,7 @@ import numpy as np
 import torch
 
 from . import (_lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxsample_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops,
-               sampletrain_ops)
+               sampletrain_ops, wideflow_ops)
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -204,6 +212,9 @@ class NormFlow(DensityEstimator):
     # freeze_bn=True) with a handful of draws per x -- through one backward launch (family `train_context_sample`); off:
     # today's per-bijector composition
     context_sample_training = False
+    # plain log_prob, inverse_and_log_det, frozen forward and sample with 17 <= num_units <= 64 as one launch at any
+    # 2 <= D <= 64 (family `wide_flow`, csrc/flow_wide.hip); off: today's wide per-layer chain or per-bijector composition
+    wide_flow = False
 
     def __init__(self, D, conditioner=False, arch_type="AR", num_stages=1, num_layers=2,
                  num_units=15, support_layer=None, device=None):
@@ -455,6 +466,22 @@ class NormFlow(DensityEstimator):
         return (inference and z.dim() == 3 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
                 and ops.flow_padded_supported(*shape))
 
+    def _wide_flow_ok(self, op, z, params, facts=None):
+        """One-launch whole-flow kernel on the exact-f32 MFMA tile (csrc/flow_wide.hip): only with the switch `wide_flow`
+        on, the conditions of `_padded_ok` (coupling, inference, a 3-d z, the fusion setting AUTO or FLOW), and a shape
+        wide_flow_supported covers (17 <= num_units <= 64, 2 <= D <= 64, the images of all 2 S layers within the LDS
+        budget).  No gradients and no fresh statistics: those calls keep their routes.  One measured exclusion (DESIGN.md
+        24, profiles/r20_wideflowbench.txt): sampling with several parameter rows at D % 8 == 0 below 32 stays on the wide
+        per-layer chain, which was faster at the one such cell measured (0.92 x at D = 8, S = 1, U = 20, 2,000 rows of 100
+        draws: each workgroup's prologue outweighs its seven tiles; 1.13 x at D = 32, S = 4)."""
+        if not getattr(self, "wide_flow", False):
+            return False
+        _, shape, _, _, _, inference = facts or self._facts(z, params)
+        if op == "forward" and params.size(0) > 1 and shape[0] % 8 == 0 and shape[0] < 32:
+            return False
+        return (inference and z.dim() == 3
+                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW) and wideflow_ops.wide_flow_supported(*shape))
+
     def _train_path(self, z, params, stats_graph=None):
         """The fused training pair of a coupling log_prob: "reversible" (whole-flow forward, one-kernel backward from
         z0), "padded" (the same pair for 2 <= D <= 63 but 32: padded whole-flow forward, the one-kernel backward at the
@@ -511,6 +538,8 @@ class NormFlow(DensityEstimator):
             return _BIJECTORS
         if self._padded_ok(z, params, f):
             return Route("padded", False, f32_draw)
+        if self._wide_flow_ok(op, z, params, f):  # before `fused`: with the switch on it takes D % 8 == 0 from the wide chain
+            return Route("wide_flow", False, False)
         if forced(z, params) if forced else self._fused_ok(z, params, f):
             whole = (f32_draw or interval) and self._whole_flow()  # the only two that ask
             return Route("fused", interval, f32_draw) if whole else _FUSED
@@ -612,6 +641,8 @@ class NormFlow(DensityEstimator):
                                                                want_log_q=route.writes_log_q)
             elif family == "context_rows":  # one wave per context; the support layer as for `padded`
                 z, sld = ctxflow_ops.ctx_flow_forward_raw(z, p_dev, *self._flow_args())
+            elif family == "wide_flow":  # one workgroup per parameter row; the support layer as for `padded`
+                z, sld = wideflow_ops.wide_flow_forward_raw(z, p_dev, *self._flow_args())
             elif family == "train_context_sample":  # one autograd node, one launch each way; the support layer as above
                 z, sld = ctxsample_ops.ctx_flow_sample_train(z, p_dev, *self._flow_args())
             elif family == "train_sample":  # one autograd node, one backward kernel; the support layer as for `padded`
@@ -667,6 +698,9 @@ class NormFlow(DensityEstimator):
         if family == "context_rows":
             return ctxflow_ops.ctx_flow_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
                                                      want_sld=want_sld)
+        if family == "wide_flow":
+            return wideflow_ops.wide_flow_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
+                                                       want_sld=want_sld)
         return ops.flow_log_prob_raw(z, params, *self._flow_args(), self.fusion, want_lp=want_lp, want_z0=want_z0,
                                      want_sld=want_sld, interval_consts=consts)
 
@@ -716,7 +750,7 @@ class NormFlow(DensityEstimator):
             # support layer first (it is the last bijector of the stack), then the core's density:
             # log q(z) = log q_core(s^-1(z)) - log|det ds| -- same sum as density_estimator.py:395-416
             z, ld_support = self.bijectors[-1].inverse_and_log_det(z)
-        if family in ("ar_fused", "padded", "fused", "context_rows"):
+        if family in ("ar_fused", "padded", "fused", "context_rows", "wide_flow"):
             log_q = self._fused_density(family, z, params, consts)[0]
         elif family == "ar_train":
             masks, mean, alpha, D, L, U = self._ar_args()
