@@ -12,7 +12,7 @@ from . import _lib, ops
 from ._lib import lib, check
 from ._staging import _home, _ptr, _rows, _stage, _stats
 
-# Contexts per workgroup of the backward kernel (csrc/flow_ctx_bwd.hip CTXT_WAVES), one wave each: the tests' edge cases.
+# Contexts per workgroup of the backward kernel (csrc/ctx_bwd_walk.h CTX_BWD_WAVES), one wave each: the tests' edge cases.
 # Where four contexts' LDS slices exceed 64 KB (large D x N) a workgroup serves one context with all four waves instead;
 # the results are the same bits either way.
 WAVES_PER_WORKGROUP = 4
