@@ -316,6 +316,21 @@ WIDEFLOW_SIGNATURES = {
                                                  _i64, _vp]),
 }
 
+# per-context coupling flows with fewer than 32 samples per context at 17 <= num_units <= 64, one launch per call each
+# way (inference and the log_prob backward), declared in include/tnf_ctxwide.h: a fifteenth table
+# (tests/test_ctx_wide_host.py)
+CTXWIDE_SIGNATURES = {
+    "tnf_ctx_wide_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i64]),
+    "tnf_ctx_wide_train_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i64]),
+    "tnf_ctx_wide_lds_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i64]),
+    "tnf_ctx_wide_launch_count": (_i64, [_i32]),
+    "tnf_ctx_wide_log_prob_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                                 _i64, _vp]),
+    "tnf_ctx_wide_forward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _vp]),
+    "tnf_ctx_wide_log_prob_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
+                                                     _i64, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -327,7 +342,7 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
                   PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES, ARSAMPLE_SIGNATURES,
-                  ARBATCH_SIGNATURES, CTXSAMPLE_SIGNATURES, WIDEFLOW_SIGNATURES):
+                  ARBATCH_SIGNATURES, CTXSAMPLE_SIGNATURES, WIDEFLOW_SIGNATURES, CTXWIDE_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

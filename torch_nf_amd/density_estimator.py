@@ -72,6 +72,11 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          when z does not require grad), 1 <= N <= 31, fusion AUTO or
                                          FLOW, ctx_train_supported (asked after the training pairs
                                          above: only calls that would otherwise compose bijectors)
+  train_context_    log_prob             wide_context_training (default off); train_context's        ctxwide_ops.ctx_wide_
+  wide                                   conditions with ctx_wide_train_supported (17 <= num_units   log_prob_train
+                                         <= 64, num_layers <= 3, the context's backward slice within
+                                         150 KB of LDS) in place of ctx_train_supported (asked right
+                                         after train_context: the unit ranges are disjoint)
   train_sample      forward (frozen)     sample_training (default off), coupling, float32, grad      sampletrain_ops.flow_
                                          mode on and params requires grad, const stats, 3-d, one     sample_train
                                          parameter row or 32 samples per row, fusion AUTO or FLOW,
@@ -91,12 +96,19 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          with N <= 5: the per-layer composition is faster there,
                                          DESIGN.md 18) (asked last: only calls that would otherwise
                                          compose bijectors)
+  context_rows_     forward (frozen),    wide_context_rows (default off); context_rows' conditions   ctxwide_ops.ctx_wide_
+  wide              log_prob, inverse    with ctx_wide_supported (17 <= num_units <= 64, num_layers  forward_raw, ctx_wide_
+                                         <= 5, one layer's operand image within 150 KB of LDS) in    log_prob_raw
+                                         place of ctx_flow_supported and without the D = 64
+                                         exception, and not (N = 1 with num_units > 48: the
+                                         composition is faster there) (asked right
+                                         after context_rows: the unit ranges are disjoint)
   bijectors         all                  everything else: the reference's loop, one kernel per       coupling, maf, affine,
                                          bijector                                                    bn_apply, bn_batch_forward
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
 a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `train_context`,
-`context_rows`, `wide_flow`, `train_sample`, `train_context_sample`, `ar_train_sample`, the batch-statistics chains (padded or not) and
+`context_rows`, `context_rows_wide`, `train_context_wide`, `wide_flow`, `train_sample`, `train_context_sample`, `ar_train_sample`, the batch-statistics chains (padded or not) and
 the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
@@ -109,8 +121,8 @@ import collections
 import numpy as np
 import torch
 
-from . import (_lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxsample_ops, ctxtrain_ops, ops, padbatch_ops, padtrain_ops,
-               sampletrain_ops, wideflow_ops)
+from . import (_lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxsample_ops, ctxtrain_ops, ctxwide_ops, ops, padbatch_ops,
+               padtrain_ops, sampletrain_ops, wideflow_ops)
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -215,6 +227,13 @@ class NormFlow(DensityEstimator):
     # plain log_prob, inverse_and_log_det, frozen forward and sample with 17 <= num_units <= 64 as one launch at any
     # 2 <= D <= 64 (family `wide_flow`, csrc/flow_wide.hip); off: today's wide per-layer chain or per-bijector composition
     wide_flow = False
+    # plain log_prob, inverse_and_log_det, frozen forward and sample with 17 <= num_units <= 64, several parameter rows
+    # and fewer than 32 samples per row as one launch (family `context_rows_wide`, csrc/flow_ctx_wide.hip); off: today's
+    # per-bijector composition
+    wide_context_rows = False
+    # the same layout's log_prob under autograd as one launch each way (family `train_context_wide`,
+    # csrc/flow_ctx_wide_bwd.hip); off: today's per-bijector composition.  Independent of `wide_context_rows`
+    wide_context_training = False
 
     def __init__(self, D, conditioner=False, arch_type="AR", num_stages=1, num_layers=2,
                  num_units=15, support_layer=None, device=None):
@@ -421,6 +440,38 @@ class NormFlow(DensityEstimator):
         return (M > 1 and (z.size(0) == M or (z.size(0) == 1 and not z.requires_grad))
                 and ctxtrain_ops.ctx_train_supported(*shape, z.size(1)))
 
+    def _wide_context_rows_ok(self, op, z, params, facts):
+        """`_context_rows_ok` above 16 units (csrc/flow_ctx_wide.hip: one workgroup per context, one layer's operand
+        image resident at a time): only with the switch `wide_context_rows` on, and exactly that predicate's conditions
+        with ctx_wide_supported (17 <= num_units <= 64) in place of ctx_flow_supported.  Its D = 64, N <= 5 exception is a
+        measurement of the 16-unit kernel and is not copied.  One measured exclusion of its own (DESIGN.md 25,
+        profiles/r22_ctxwidebench.txt; M N = 2^16, S = 2, L = 2): ONE sample per context above 48 units, every op, where a
+        workgroup builds every layer's 70 .. 134 KB image for a single row of z and the composition's per-layer kernels
+        stream the same parameters faster (0.89 .. 0.98 x at num_units = 64, D = 4 .. 64; 1.27 .. 1.59 x at N = 8).  The C
+        entries accept the class all the same."""
+        arch, shape, stats_graph, _, plain, _ = facts
+        if not (getattr(self, "wide_context_rows", False) and arch == "coupling" and plain and not stats_graph
+                and z.dim() == 3 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
+            return False
+        M = params.size(0)
+        if z.size(1) == 1 and shape[3] > 48:
+            return False
+        return (M > 1 and z.size(0) in ((M,) if op == "forward" else (1, M))
+                and ctxwide_ops.ctx_wide_supported(*shape, z.size(1)))
+
+    def _wide_context_train_ok(self, z, params, facts):
+        """`_context_train_ok` above 16 units (csrc/flow_ctx_wide.hip forward keeping z0, csrc/flow_ctx_wide_bwd.hip
+        backward): only with the switch `wide_context_training` on (independent of every other switch), and exactly that
+        predicate's conditions with ctx_wide_train_supported in place of ctx_train_supported."""
+        arch, shape, stats_graph, f32, _, _ = facts
+        if not (getattr(self, "wide_context_training", False) and arch == "coupling" and f32 and torch.is_grad_enabled()
+                and (params.requires_grad or z.requires_grad) and not stats_graph and z.dim() == 3
+                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
+            return False
+        M = params.size(0)
+        return (M > 1 and (z.size(0) == M or (z.size(0) == 1 and not z.requires_grad))
+                and ctxwide_ops.ctx_wide_train_supported(*shape, z.size(1)))
+
     def _sample_train_ok(self, z, params, facts):
         """One launch forward, one walk kernel backward for frozen-statistics sampling under autograd
         (csrc/flow_bwd_f16.hip, flow_sample_bwd_kernel): only with the switch `sample_training` on, a coupling stack,
@@ -549,12 +600,16 @@ class NormFlow(DensityEstimator):
                 return Route("train_" + pair, False, False)
         if op == "log_prob" and self._context_train_ok(z, params, f):
             return Route("train_context", False, False)
+        if op == "log_prob" and self._wide_context_train_ok(z, params, f):  # 17 .. 64 units: disjoint from the above
+            return Route("train_context_wide", False, False)
         if op == "forward" and self._sample_train_ok(z, params, f):
             return Route("train_sample", False, f32_draw)
         if op == "forward" and self._context_sample_train_ok(z, params, f):
             return Route("train_context_sample", False, False)
         if self._context_rows_ok(op, z, params, f):  # asked last: nothing another family takes changes hands
             return Route("context_rows", False, False)
+        if self._wide_context_rows_ok(op, z, params, f):  # 17 .. 64 units: disjoint from the above
+            return Route("context_rows_wide", False, False)
         return _BIJECTORS
 
     # -- sampling -----------------------------------------------------------
@@ -641,6 +696,8 @@ class NormFlow(DensityEstimator):
                                                                want_log_q=route.writes_log_q)
             elif family == "context_rows":  # one wave per context; the support layer as for `padded`
                 z, sld = ctxflow_ops.ctx_flow_forward_raw(z, p_dev, *self._flow_args())
+            elif family == "context_rows_wide":  # one workgroup per context; the support layer as for `padded`
+                z, sld = ctxwide_ops.ctx_wide_forward_raw(z, p_dev, *self._flow_args())
             elif family == "wide_flow":  # one workgroup per parameter row; the support layer as for `padded`
                 z, sld = wideflow_ops.wide_flow_forward_raw(z, p_dev, *self._flow_args())
             elif family == "train_context_sample":  # one autograd node, one launch each way; the support layer as above
@@ -698,6 +755,9 @@ class NormFlow(DensityEstimator):
         if family == "context_rows":
             return ctxflow_ops.ctx_flow_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
                                                      want_sld=want_sld)
+        if family == "context_rows_wide":
+            return ctxwide_ops.ctx_wide_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
+                                                     want_sld=want_sld)
         if family == "wide_flow":
             return wideflow_ops.wide_flow_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
                                                        want_sld=want_sld)
@@ -750,7 +810,7 @@ class NormFlow(DensityEstimator):
             # support layer first (it is the last bijector of the stack), then the core's density:
             # log q(z) = log q_core(s^-1(z)) - log|det ds| -- same sum as density_estimator.py:395-416
             z, ld_support = self.bijectors[-1].inverse_and_log_det(z)
-        if family in ("ar_fused", "padded", "fused", "context_rows", "wide_flow"):
+        if family in ("ar_fused", "padded", "fused", "context_rows", "context_rows_wide", "wide_flow"):
             log_q = self._fused_density(family, z, params, consts)[0]
         elif family == "ar_train":
             masks, mean, alpha, D, L, U = self._ar_args()
@@ -759,6 +819,8 @@ class NormFlow(DensityEstimator):
             log_q = padtrain_ops.flow_padded_log_prob_train(z, params, *self._flow_args())
         elif family == "train_context":  # ... per-context rows with fewer than 32 samples each: one launch each way
             log_q = ctxtrain_ops.ctx_flow_log_prob_train(z, params, *self._flow_args())
+        elif family == "train_context_wide":  # ... the same at 17 <= num_units <= 64
+            log_q = ctxwide_ops.ctx_wide_log_prob_train(z, params, *self._flow_args())
         elif family != "bijectors":  # training with the BatchNorm statistics constant, one of the two fused pairs
             log_q = ops.flow_log_prob_train(z, params, *self._flow_args(), reversible=family == "train_reversible")
         else:
