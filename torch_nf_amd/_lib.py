@@ -331,6 +331,18 @@ CTXWIDE_SIGNATURES = {
                                                      _i64, _i64, _vp]),
 }
 
+# the same layout trained through its frozen-statistics samples: the backward of tnf_ctx_wide_forward_f32 in one launch,
+# with a process-wide override of the workgroup's team size, declared in include/tnf_ctxwidesample.h
+# (tests/test_ctx_wide_sample_host.py).  Not a `*_SIGNATURES` table: those are a closed set of fifteen
+CTXWIDESAMPLE_ENTRIES = {
+    "tnf_ctx_wide_sample_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i64]),
+    "tnf_ctx_wide_sample_launch_count": (_i64, []),
+    "tnf_ctx_wide_sample_waves": (ctypes.c_int, [_i32, _i32, _i64]),
+    "tnf_ctx_wide_sample_set_waves": (ctypes.c_int, [_i32]),
+    "tnf_ctx_wide_sample_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32,
+                                                   _i32, _i64, _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -342,7 +354,8 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
                   PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES, ARSAMPLE_SIGNATURES,
-                  ARBATCH_SIGNATURES, CTXSAMPLE_SIGNATURES, WIDEFLOW_SIGNATURES, CTXWIDE_SIGNATURES):
+                  ARBATCH_SIGNATURES, CTXSAMPLE_SIGNATURES, WIDEFLOW_SIGNATURES, CTXWIDE_SIGNATURES,
+                  CTXWIDESAMPLE_ENTRIES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

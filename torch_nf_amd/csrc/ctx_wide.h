@@ -30,4 +30,17 @@ inline bool ctx_wide_train_supported(int D, int S, int L, int U, int64_t N) {
     return ctx_wide_domain(D, S, U, N) && L >= 1 && L <= 3 && ctx_wide_lds_bytes(1, D, S, L, U, N) <= kCtxWideLdsBudget;
 }
 
+// The team size of a backward launch (flow_ctx_wide_bwd.hip, flow_ctx_wide_sample_bwd.hip; host code), measured at 4, 8
+// and 16 waves (profiles/r22_ctxwidebench_waves.txt).  The
+// widest steps of the walk are the weight-gradient contractions, 2 U U items (2 U ceil(D / 2) for the first and last
+// layer): where they have at most 1,024 items (20 units below D = 64) four waves are 1.1 .. 1.3 x faster than eight, above
+// that eight are 1.2 .. 1.5 x faster than four; sixteen win, 1.4 .. 1.5 x over eight, only in the one class where every
+// step is wide -- two tiles of samples, more than 48 units and D >= 32 -- and lose 1.1 .. 1.8 x elsewhere.  33 .. 48
+// units were not measured and follow the item count.  The results are the same bits for every team size.
+inline int cwb_waves(int N, int D, int U) {
+    if (N > 16 && U > 48 && D >= 32) return 16;
+    const int widest = 2 * U * (U > (D + 1) / 2 ? U : (D + 1) / 2);
+    return widest <= 1024 ? 4 : 8;
+}
+
 }  // namespace tnf

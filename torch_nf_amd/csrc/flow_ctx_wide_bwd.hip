@@ -20,17 +20,7 @@ namespace tnf {
 
 constexpr int CWB_MAX_WAVES = 16;  // the team is the launch's block: 4, 8 or 16 waves, all on one context
 
-// The team size of a shape, measured at 4, 8 and 16 waves (profiles/r22_ctxwidebench_waves.txt).  The
-// widest steps of the walk are the weight-gradient contractions, 2 U U items (2 U ceil(D / 2) for the first and last
-// layer): where they have at most 1,024 items (20 units below D = 64) four waves are 1.1 .. 1.3 x faster than eight, above
-// that eight are 1.2 .. 1.5 x faster than four; sixteen win, 1.4 .. 1.5 x over eight, only in the one class where every
-// step is wide -- two tiles of samples, more than 48 units and D >= 32 -- and lose 1.1 .. 1.8 x elsewhere.  33 .. 48
-// units were not measured and follow the item count.  The results are the same bits for every team size.
-static int cwb_waves(int N, int D, int U) {
-    if (N > 16 && U > 48 && D >= 32) return 16;
-    const int widest = 2 * U * (U > (D + 1) / 2 ? U : (D + 1) / 2);
-    return widest <= 1024 ? 4 : 8;
-}
+// the team size of a shape: cwb_waves (ctx_wide.h)
 
 extern std::atomic<long long> g_ctxwide_launches[TNF_CTXWIDE_COUNTERS];  // flow_ctx_wide.hip
 

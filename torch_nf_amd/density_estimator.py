@@ -89,6 +89,14 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          (asked after train_sample, which takes one parameter row
                                          or 32 samples per row; independent of context_rows and
                                          context_training)
+  train_context_    forward (frozen)     wide_context_sample_training (default off);                 ctxwidesample_ops.ctx_
+  sample_wide                            train_context_sample's conditions with                      wide_sample_train
+                                         ctx_wide_sample_supported (17 <= num_units <= 64,
+                                         num_layers <= 3, one layer's operand image and the
+                                         context's backward slice within 150 KB of LDS) in place of
+                                         ctx_sample_supported (asked right after
+                                         train_context_sample: the unit ranges are disjoint;
+                                         independent of every other switch)
   context_rows      forward (frozen),    context_rows (default off), coupling, plain, const stats,   ctxflow_ops.ctx_flow_
                     log_prob, inverse    3-d, several parameter rows = the larger batch, M_z = 1 or  forward_raw, ctx_flow_
                                          M (forward: M), 1 <= N <= 31, fusion AUTO or FLOW,          log_prob_raw
@@ -108,7 +116,7 @@ only the per-bijector composition differentiates through them); "not few" = not 
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
 a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `train_context`,
-`context_rows`, `context_rows_wide`, `train_context_wide`, `wide_flow`, `train_sample`, `train_context_sample`, `ar_train_sample`, the batch-statistics chains (padded or not) and
+`context_rows`, `context_rows_wide`, `train_context_wide`, `wide_flow`, `train_sample`, `train_context_sample`, `train_context_sample_wide`, `ar_train_sample`, the batch-statistics chains (padded or not) and
 the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
@@ -121,8 +129,8 @@ import collections
 import numpy as np
 import torch
 
-from . import (_lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxsample_ops, ctxtrain_ops, ctxwide_ops, ops, padbatch_ops,
-               padtrain_ops, sampletrain_ops, wideflow_ops)
+from . import (_lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxsample_ops, ctxtrain_ops, ctxwide_ops, ctxwidesample_ops, ops,
+               padbatch_ops, padtrain_ops, sampletrain_ops, wideflow_ops)
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -234,6 +242,10 @@ class NormFlow(DensityEstimator):
     # the same layout's log_prob under autograd as one launch each way (family `train_context_wide`,
     # csrc/flow_ctx_wide_bwd.hip); off: today's per-bijector composition.  Independent of `wide_context_rows`
     wide_context_training = False
+    # the same layout's frozen-statistics sampling under autograd -- cde(x, N, freeze_bn=True) with a handful of draws per
+    # x, then loss(z, log_q).backward() -- as one launch each way (family `train_context_sample_wide`,
+    # csrc/flow_ctx_wide_sample_bwd.hip); off: today's per-bijector composition.  Independent of every other switch
+    wide_context_sample_training = False
 
     def __init__(self, D, conditioner=False, arch_type="AR", num_stages=1, num_layers=2,
                  num_units=15, support_layer=None, device=None):
@@ -497,6 +509,19 @@ class NormFlow(DensityEstimator):
         M = params.size(0)
         return M > 1 and z.size(0) == M and ctxsample_ops.ctx_sample_supported(*shape, z.size(1))
 
+    def _wide_context_sample_train_ok(self, z, params, facts):
+        """`_context_sample_train_ok` above 16 units (csrc/flow_ctx_wide.hip forward, csrc/flow_ctx_wide_sample_bwd.hip
+        backward): only with the switch `wide_context_sample_training` on (independent of every other switch), and exactly
+        that predicate's conditions with ctx_wide_sample_supported in place of ctx_sample_supported.  The inference
+        exclusion of `_wide_context_rows_ok` (N = 1 above 48 units) is a measurement of another op and is not copied."""
+        arch, shape, stats_graph, f32, _, _ = facts
+        if not (getattr(self, "wide_context_sample_training", False) and arch == "coupling" and f32
+                and torch.is_grad_enabled() and params.requires_grad and not stats_graph and z.dim() == 3
+                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
+            return False
+        M = params.size(0)
+        return M > 1 and z.size(0) == M and ctxwidesample_ops.ctx_wide_sample_supported(*shape, z.size(1))
+
     def _stats_in_graph(self):
         """Do the cached BatchNorm statistics still carry the graph of the batch-mode forward that produced them
         (per-bijector forward under autograd -- the reference's behaviour, bijectors.py:414-415)?  Then every later
@@ -606,6 +631,8 @@ class NormFlow(DensityEstimator):
             return Route("train_sample", False, f32_draw)
         if op == "forward" and self._context_sample_train_ok(z, params, f):
             return Route("train_context_sample", False, False)
+        if op == "forward" and self._wide_context_sample_train_ok(z, params, f):  # 17 .. 64 units: disjoint from the above
+            return Route("train_context_sample_wide", False, False)
         if self._context_rows_ok(op, z, params, f):  # asked last: nothing another family takes changes hands
             return Route("context_rows", False, False)
         if self._wide_context_rows_ok(op, z, params, f):  # 17 .. 64 units: disjoint from the above
@@ -702,6 +729,8 @@ class NormFlow(DensityEstimator):
                 z, sld = wideflow_ops.wide_flow_forward_raw(z, p_dev, *self._flow_args())
             elif family == "train_context_sample":  # one autograd node, one launch each way; the support layer as above
                 z, sld = ctxsample_ops.ctx_flow_sample_train(z, p_dev, *self._flow_args())
+            elif family == "train_context_sample_wide":  # the same above 16 units: one workgroup per context each way
+                z, sld = ctxwidesample_ops.ctx_wide_sample_train(z, p_dev, *self._flow_args())
             elif family == "train_sample":  # one autograd node, one backward kernel; the support layer as for `padded`
                 z, sld, *written = sampletrain_ops.flow_sample_train(z, p_dev, *self._flow_args(), self.fusion,
                                                                      want_log_q=route.writes_log_q)
