@@ -648,4 +648,5 @@ int tnf_ef_dot_backward(int32_t dtype, int32_t family, const void* z, const void
 #include "tnf_wideflow.h"    /* the whole coupling flow in one launch at 17 <= num_units <= 64, any D <= 64: the same */
 #include "tnf_ctxwide.h"     /* per-context flows with fewer than 32 samples each at 17 <= num_units <= 64, both ways: the same */
 #include "tnf_ctxwidesample.h" /* the same flows trained through their samples, one backward launch: the same */
+#include "tnf_widestream.h"    /* the whole coupling flow at 17 <= num_units <= 64 with any number of stages: the same */
 #endif /* TNF_H */

@@ -343,6 +343,21 @@ CTXWIDESAMPLE_ENTRIES = {
                                                    _i32, _i64, _i64, _vp]),
 }
 
+# the whole coupling flow at 17 <= num_units <= 64 with any number of stages, one layer's operand image streamed through
+# LDS at a time, declared in include/tnf_widestream.h (tests/test_wide_stream_host.py).  Not a `*_SIGNATURES` table
+# either, for the same reason
+WIDESTREAM_ENTRIES = {
+    "tnf_wide_flow_stream_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "tnf_wide_flow_stream_lds_bytes": (_i64, [_i32, _i32, _i32]),
+    "tnf_wide_flow_stream_tiles": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i64, _i64]),
+    "tnf_wide_flow_stream_set_tiles": (ctypes.c_int, [_i32]),
+    "tnf_wide_flow_stream_launch_count": (_i64, [_i32]),
+    "tnf_wide_flow_stream_log_prob_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32,
+                                                         _i32, _i64, _vp]),
+    "tnf_wide_flow_stream_forward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                                        _i64, _vp]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -355,7 +370,7 @@ def _load():
     for table in (SIGNATURES, MOG_SIGNATURES, ABC_SIGNATURES, HEBB_SIGNATURES, EFN_SIGNATURES, PADTRAIN_SIGNATURES,
                   PADBATCH_SIGNATURES, CTXFLOW_SIGNATURES, CTXTRAIN_SIGNATURES, SAMPLETRAIN_SIGNATURES, ARSAMPLE_SIGNATURES,
                   ARBATCH_SIGNATURES, CTXSAMPLE_SIGNATURES, WIDEFLOW_SIGNATURES, CTXWIDE_SIGNATURES,
-                  CTXWIDESAMPLE_ENTRIES):
+                  CTXWIDESAMPLE_ENTRIES, WIDESTREAM_ENTRIES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError here = header / library out of step
             fn.restype = res

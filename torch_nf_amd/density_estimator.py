@@ -55,6 +55,17 @@ only the per-bijector composition differentiates through them); "not few" = not 
                                          faster there) (asked before fused: with the
                                          switch on it takes the D % 8 == 0 shapes from the wide
                                          per-layer chain)
+  wide_flow_        forward (frozen),    wide_flow_streamed (default off); wide_flow's conditions    widestream_ops.wide_flow_
+  streamed          log_prob, inverse    with wide_flow_supported 0 and wide_flow_stream_supported   stream_forward_raw, wide_
+                                         1 (17 <= num_units <= 64, any 2 <= D <= 64, ONE layer's     flow_stream_log_prob_raw
+                                         operand image within the LDS budget, 1 <= S <= 1024: the
+                                         stage counts the resident kernel cannot hold), and not
+                                         (D % 8 == 0 unless z and params are one row each with
+                                         N <= 2^17, forward: N <= 2^12: the wide per-layer chain
+                                         is faster or ties beyond)
+                                         (wide_flow's own sampling exclusion is not copied; asked
+                                         right after wide_flow: the shape sets are disjoint
+                                         whatever the switches say)
   fused             forward (frozen),    coupling, plain, const stats, not few, has_fast_path        flow_forward_raw,
                     log_prob, inverse    (`_fused_ok`; whole flow or per-layer chain as `fusion`     flow_log_prob_raw
                                          resolves)
@@ -116,7 +127,7 @@ only the per-bijector composition differentiates through them); "not few" = not 
 
 Support layer (ToInterval / ToSimplex, the last bijector).  ar_fused, ar_train and the whole-flow `fused` kernel evaluate
 a ToInterval layer in their own load / store stage (`Route.fuse_support`); `padded`, `train_padded`, `train_context`,
-`context_rows`, `context_rows_wide`, `train_context_wide`, `wide_flow`, `train_sample`, `train_context_sample`, `train_context_sample_wide`, `ar_train_sample`, the batch-statistics chains (padded or not) and
+`context_rows`, `context_rows_wide`, `train_context_wide`, `wide_flow`, `wide_flow_streamed`, `train_sample`, `train_context_sample`, `train_context_sample_wide`, `ar_train_sample`, the batch-statistics chains (padded or not) and
 the per-layer chain do not.
 Otherwise it is one extra elementwise kernel: after the stack in `forward`, before the core route in `log_prob`.
 `inverse_and_log_det` of a flow with a support layer is always `bijectors` over the whole stack.
@@ -130,7 +141,7 @@ import numpy as np
 import torch
 
 from . import (_lib, arbatch_ops, arsample_ops, ctxflow_ops, ctxsample_ops, ctxtrain_ops, ctxwide_ops, ctxwidesample_ops, ops,
-               padbatch_ops, padtrain_ops, sampletrain_ops, wideflow_ops)
+               padbatch_ops, padtrain_ops, sampletrain_ops, wideflow_ops, widestream_ops)
 from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 
 
@@ -235,6 +246,10 @@ class NormFlow(DensityEstimator):
     # plain log_prob, inverse_and_log_det, frozen forward and sample with 17 <= num_units <= 64 as one launch at any
     # 2 <= D <= 64 (family `wide_flow`, csrc/flow_wide.hip); off: today's wide per-layer chain or per-bijector composition
     wide_flow = False
+    # the same calls at the stage counts that kernel cannot hold in LDS -- S > 4, 2, 1 or 0 by shape -- as one launch with
+    # the layers' operand images streamed through LDS (family `wide_flow_streamed`, csrc/flow_wide_stream.hip); off:
+    # today's wide per-layer chain or per-bijector composition.  Independent of `wide_flow`: the shape sets are disjoint
+    wide_flow_streamed = False
     # plain log_prob, inverse_and_log_det, frozen forward and sample with 17 <= num_units <= 64, several parameter rows
     # and fewer than 32 samples per row as one launch (family `context_rows_wide`, csrc/flow_ctx_wide.hip); off: today's
     # per-bijector composition
@@ -558,6 +573,28 @@ class NormFlow(DensityEstimator):
         return (inference and z.dim() == 3
                 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW) and wideflow_ops.wide_flow_supported(*shape))
 
+    def _wide_flow_stream_ok(self, op, z, params, facts=None):
+        """One-launch whole-flow kernel with the layers' operand images streamed through LDS (csrc/flow_wide_stream.hip):
+        only with the switch `wide_flow_streamed` on, the conditions of `_wide_flow_ok` (coupling, inference, a 3-d z, the
+        fusion setting AUTO or FLOW; no gradients, no fresh statistics), a shape wide_flow_supported does NOT cover --
+        so the two families are disjoint whatever the switches say -- and one wide_flow_stream_supported does
+        (17 <= num_units <= 64, 2 <= D <= 64, one layer's image within the LDS budget, S <= 1024).  One measured
+        exclusion (profiles/r24_widestreambench.txt): at D % 8 == 0, where the switch-off route is the wide
+        per-layer chain, the kernel wins every measured cell with one row of up to 2^17 samples in log_prob (1.07 .. 1.68 x
+        over four shapes at 2^12 and 2^17) and of 2^12 in sampling (1.06 .. 1.59 x), and loses cells of every other class
+        -- sampling, one row of 2^17: 0.98 x at (64, 4, 2, 64); one row of 2^20 samples: 0.76 .. 1.01 x (64, 4, 2, 64:
+        0.81 / 0.76); 2,000 rows of 100: 0.75 .. 1.27 x (64, 4, 2, 32: 0.75) -- so D % 8 == 0 is taken only with one block
+        of z, one parameter row and N <= 2^17 (forward: N <= 2^12).  Every other D wins all its cells (2.5 .. 11.5 x the
+        composition)."""
+        if not getattr(self, "wide_flow_streamed", False):
+            return False
+        _, shape, _, _, _, inference = facts or self._facts(z, params)
+        if shape[0] % 8 == 0:  # against the wide per-layer chain: one block of z, one parameter row, N up to the measured win
+            if not (z.dim() == 3 and z.size(0) == 1 and params.size(0) == 1 and z.size(1) <= 1 << (12 if op == "forward" else 17)):
+                return False
+        return (inference and z.dim() == 3 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
+                and not wideflow_ops.wide_flow_supported(*shape) and widestream_ops.wide_flow_stream_supported(*shape))
+
     def _train_path(self, z, params, stats_graph=None):
         """The fused training pair of a coupling log_prob: "reversible" (whole-flow forward, one-kernel backward from
         z0), "padded" (the same pair for 2 <= D <= 63 but 32: padded whole-flow forward, the one-kernel backward at the
@@ -616,6 +653,8 @@ class NormFlow(DensityEstimator):
             return Route("padded", False, f32_draw)
         if self._wide_flow_ok(op, z, params, f):  # before `fused`: with the switch on it takes D % 8 == 0 from the wide chain
             return Route("wide_flow", False, False)
+        if self._wide_flow_stream_ok(op, z, params, f):  # the stage counts `wide_flow` cannot hold: disjoint from it
+            return Route("wide_flow_streamed", False, False)
         if forced(z, params) if forced else self._fused_ok(z, params, f):
             whole = (f32_draw or interval) and self._whole_flow()  # the only two that ask
             return Route("fused", interval, f32_draw) if whole else _FUSED
@@ -727,6 +766,8 @@ class NormFlow(DensityEstimator):
                 z, sld = ctxwide_ops.ctx_wide_forward_raw(z, p_dev, *self._flow_args())
             elif family == "wide_flow":  # one workgroup per parameter row; the support layer as for `padded`
                 z, sld = wideflow_ops.wide_flow_forward_raw(z, p_dev, *self._flow_args())
+            elif family == "wide_flow_streamed":  # the same with the layers' images streamed through LDS
+                z, sld = widestream_ops.wide_flow_stream_forward_raw(z, p_dev, *self._flow_args())
             elif family == "train_context_sample":  # one autograd node, one launch each way; the support layer as above
                 z, sld = ctxsample_ops.ctx_flow_sample_train(z, p_dev, *self._flow_args())
             elif family == "train_context_sample_wide":  # the same above 16 units: one workgroup per context each way
@@ -790,6 +831,9 @@ class NormFlow(DensityEstimator):
         if family == "wide_flow":
             return wideflow_ops.wide_flow_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
                                                        want_sld=want_sld)
+        if family == "wide_flow_streamed":
+            return widestream_ops.wide_flow_stream_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp,
+                                                                want_z0=want_z0, want_sld=want_sld)
         return ops.flow_log_prob_raw(z, params, *self._flow_args(), self.fusion, want_lp=want_lp, want_z0=want_z0,
                                      want_sld=want_sld, interval_consts=consts)
 
@@ -839,7 +883,8 @@ class NormFlow(DensityEstimator):
             # support layer first (it is the last bijector of the stack), then the core's density:
             # log q(z) = log q_core(s^-1(z)) - log|det ds| -- same sum as density_estimator.py:395-416
             z, ld_support = self.bijectors[-1].inverse_and_log_det(z)
-        if family in ("ar_fused", "padded", "fused", "context_rows", "context_rows_wide", "wide_flow"):
+        if family in ("ar_fused", "padded", "fused", "context_rows", "context_rows_wide", "wide_flow",
+                      "wide_flow_streamed"):
             log_q = self._fused_density(family, z, params, consts)[0]
         elif family == "ar_train":
             masks, mean, alpha, D, L, U = self._ar_args()
