@@ -4,12 +4,8 @@ parameter row per context and 1 <= N <= 31 samples per context, the whole flow i
 `ctx_flow_log_prob_raw` and `ctx_flow_forward_raw` are the entries NormFlow routes to (family `context_rows`, behind the
 switch `NormFlow.context_rows`); they return what ops.flow_padded_log_prob_raw and ops.flow_padded_forward_raw return.
 No autograd: calls that need gradients keep their routes."""
-import torch
-
-from . import _lib
-from ._lib import lib, check
-from ._staging import _home, _ptr
-from .ops import _empty_f32, _flow_prep
+from . import _flow_family
+from ._lib import lib
 
 WAVES_PER_WORKGROUP = 4  # contexts per workgroup of the kernel (csrc/flow_ctx.hip CTX_WAVES): the tests' edge cases
 COUNT_LOG_PROB, COUNT_FORWARD = 0, 1  # TNF_CTXFLOW_COUNT_*
@@ -28,25 +24,12 @@ def launch_counts():
 def ctx_flow_log_prob_raw(z, params, bn_mean, bn_alpha, D, S, L, U, want_lp=True, want_z0=False, want_sld=False):
     """tnf_ctx_flow_log_prob_f32: z (M_z, N, D) with M_z in {1, M}, params (M, >= D_params) one row per context
     -> (log_prob | None, z0 | None, sum_log_det | None), one launch."""
-    dev, zc, pc, pstride, mean_c, alpha_c, Mz, Mp, M, N = _flow_prep(z, params, bn_mean, bn_alpha)
-    if zc.shape[2] != D:
-        raise ValueError("last dimension of z (%d) must equal D (%d)" % (zc.shape[2], D))
-    lp, z0, sld = _empty_f32(want_lp, (M, N), dev), _empty_f32(want_z0, (M, N, D), dev), _empty_f32(want_sld, (M, N), dev)
-    check(lib.tnf_ctx_flow_log_prob_f32(zc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(), _ptr(lp),
-                                        _ptr(z0), _ptr(sld), Mz, Mp, N, D, S, L, U, pstride, _lib.stream_ptr()))
-    return _home((lp, z0, sld), z.device, dev)
+    return _flow_family.log_prob_raw("tnf_ctx_flow_log_prob_f32", z, params, bn_mean, bn_alpha, D, S, L, U, want_lp, want_z0,
+                                     want_sld)
 
 
 def ctx_flow_forward_raw(omega, params, bn_mean, bn_alpha, D, S, L, U):
     """tnf_ctx_flow_forward_f32 (frozen BatchNorm): omega (M, N, D), params (M, >= D_params)
     -> (z (M, N, D), sum_log_det (M, N)), one launch.  The caller forms log_q = log N(omega; 0, I) - sum_log_det."""
-    dev, oc, pc, pstride, mean_c, alpha_c, Mz, Mp, M, N = _flow_prep(omega, params, bn_mean, bn_alpha)
-    if oc.shape[2] != D:
-        raise ValueError("last dimension of omega (%d) must equal D (%d)" % (oc.shape[2], D))
-    if Mz != Mp:
-        raise RuntimeError("sampling needs one block of omega per parameter row (%d and %d)" % (Mz, Mp))
-    z_out = torch.empty((M, N, D), dtype=torch.float32, device=dev)
-    sld = torch.empty((M, N), dtype=torch.float32, device=dev)
-    check(lib.tnf_ctx_flow_forward_f32(oc.data_ptr(), pc.data_ptr(), mean_c.data_ptr(), alpha_c.data_ptr(),
-                                       z_out.data_ptr(), sld.data_ptr(), M, N, D, S, L, U, pstride, _lib.stream_ptr()))
-    return _home((z_out, sld), omega.device, dev)
+    return _flow_family.forward_raw("tnf_ctx_flow_forward_f32", omega, params, bn_mean, bn_alpha, D, S, L, U,
+                                    shared_params=False)

@@ -10,7 +10,10 @@ Execution: `NormFlow._route` names the kernel family of every call; each public 
 once and runs that one arm.  First match wins, top to bottom.  "plain" = z and params float32 and, with grad mode on,
 neither requires grad; "const stats" = the cached BatchNorm statistics carry no graph (`_stats_in_graph()` is False:
 only the per-bijector composition differentiates through them); "not few" = not (several parameter rows and fewer than
-32 samples each); "3-d" = z is (M, N, D).
+32 samples each); "3-d" = z is (M, N, D).  The entries that take (z, params, statistics, shape) and nothing else are
+reached through one lookup per operation (`_SAMPLERS`, `_DENSITIES`, `_TRAINERS`: family -> module, attribute) where
+they belong to the seven one-launch coupling families; the per-context families up to 16 units and their `_wide` twins
+share a predicate each, asked twice (`_PER_CONTEXT`: switch -> `*_supported` function, measured exclusion).
 
   family            offered to           conditions                                                  ops entry
   ----------------  -------------------  ----------------------------------------------------------  --------------------
@@ -149,6 +152,58 @@ from .bijectors import MAF, Affine, BatchNorm, Bijector, RealNVP, _Checked
 # writes log_q itself
 Route = collections.namedtuple("Route", "family fuse_support writes_log_q")
 _BIJECTORS, _FUSED = Route("bijectors", False, False), Route("fused", False, False)  # the two commonest, built once
+
+# The arms of the seven one-launch coupling families, which all take (z, params, *NormFlow._flow_args()) and nothing else,
+# per operation: family -> (module, attribute), resolved with getattr when the call is made (the host tests replace
+# `module.attribute` by recorders).
+# None of them evaluates a support layer: it runs as its own kernel.
+_SAMPLERS = {  # NormFlow._forward_from, frozen statistics -> (z, sum_log_det)
+    "context_rows": (ctxflow_ops, "ctx_flow_forward_raw"),  # one wave per context
+    "context_rows_wide": (ctxwide_ops, "ctx_wide_forward_raw"),  # one workgroup per context
+    "wide_flow": (wideflow_ops, "wide_flow_forward_raw"),  # one workgroup per parameter row
+    "wide_flow_streamed": (widestream_ops, "wide_flow_stream_forward_raw"),  # ... the layers' images streamed through LDS
+    "train_context_sample": (ctxsample_ops, "ctx_flow_sample_train"),  # one autograd node, one launch each way
+    "train_context_sample_wide": (ctxwidesample_ops, "ctx_wide_sample_train"),  # ... above 16 units
+}
+_DENSITIES = {  # NormFlow._fused_density (want_lp, want_z0, want_sld) -> (log_prob | None, z0 | None, sum_log_det | None)
+    "context_rows": (ctxflow_ops, "ctx_flow_log_prob_raw"),
+    "context_rows_wide": (ctxwide_ops, "ctx_wide_log_prob_raw"),
+    "wide_flow": (wideflow_ops, "wide_flow_log_prob_raw"),
+    "wide_flow_streamed": (widestream_ops, "wide_flow_stream_log_prob_raw"),
+}
+_TRAINERS = {  # NormFlow.log_prob under autograd, the BatchNorm statistics constant -> log_prob
+    "train_context": (ctxtrain_ops, "ctx_flow_log_prob_train"),  # per-context rows, fewer than 32 samples each
+    "train_context_wide": (ctxwide_ops, "ctx_wide_log_prob_train"),  # ... at 17 <= num_units <= 64
+}
+
+
+def _context_rows_slower(op, shape, N):
+    """The measured exclusion of `context_rows` (profiles/r14_ctxbench.txt): the inverse direction at
+    D = 64 with at most 5 samples per context stays on the composition, whose fp32-MFMA layer kernel is faster there
+    (0.82 x at N = 1 .. 0.97 x at N = 4; 1.07 x at N = 6)."""
+    return op != "forward" and shape[0] == 64 and N <= 5
+
+
+def _context_rows_wide_slower(op, shape, N):
+    """The measured exclusion of `context_rows_wide` (profiles/r22_ctxwidebench.txt; M N = 2^16, S = 2,
+    L = 2): ONE sample per context above 48 units, every op, where a workgroup builds every layer's 70 .. 134 KB image
+    for a single row of z and the composition's per-layer kernels stream the same parameters faster (0.89 .. 0.98 x at
+    num_units = 64, D = 4 .. 64; 1.27 .. 1.59 x at N = 8).  The C entries accept the class all the same.  The D = 64,
+    N <= 5 exception of `context_rows` is a measurement of the 16-unit kernel and is not copied."""
+    return N == 1 and shape[3] > 48
+
+
+# What `NormFlow._route` asks each per-context predicate with, twice: switch -> (module, its `*_supported` function by
+# name, the family's measured exclusion or None).  Read only once the switch has tested true, with getattr at that time:
+# with a switch off, the call costs that one test.
+_PER_CONTEXT = {
+    "context_rows": (ctxflow_ops, "ctx_flow_supported", _context_rows_slower),
+    "wide_context_rows": (ctxwide_ops, "ctx_wide_supported", _context_rows_wide_slower),
+    "context_training": (ctxtrain_ops, "ctx_train_supported", None),
+    "wide_context_training": (ctxwide_ops, "ctx_wide_train_supported", None),
+    "context_sample_training": (ctxsample_ops, "ctx_sample_supported", None),
+    "wide_context_sample_training": (ctxwidesample_ops, "ctx_wide_sample_supported", None),
+}
 
 
 def _min_two(val):
@@ -433,71 +488,44 @@ class NormFlow(DensityEstimator):
                 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
                 and padbatch_ops.flow_padded_batch_supported(self.D, self.num_stages, self.num_layers, self.num_units))
 
-    def _context_rows_ok(self, op, z, params, facts):
-        """One launch for a per-context call with fewer than 32 samples per context (csrc/flow_ctx.hip): only with the
-        switch `context_rows` on, a coupling stack, plain, constant statistics, a 3-d z, several parameter rows that
-        are the larger batch, one block of z rows for all contexts or one per context (sampling: one per context), and
-        the fusion setting AUTO or FLOW as for the `padded` family.  One measured exception (DESIGN.md 18,
-        profiles/r14_ctxbench.txt): the inverse direction at D = 64 with at most 5 samples per context stays on the
-        composition, whose fp32-MFMA layer kernel is faster there (0.82 x at N = 1 .. 0.97 x at N = 4; 1.07 x at N = 6).
-        No gradients: calls under autograd keep their routes, or take `train_context` with its own switch on."""
+    def _context_rows_ok(self, op, z, params, facts, switch):
+        """One launch for a per-context call with fewer than 32 samples per context: only with the switch named on, a
+        coupling stack, plain, constant statistics, a 3-d z, several parameter rows that are the larger batch, one block
+        of z rows for all contexts or one per context (sampling: one per context), the fusion setting AUTO or FLOW as for
+        the `padded` family, a shape the `*_supported` function of `_PER_CONTEXT[switch]` covers, and not its measured
+        exclusion `slower(op, shape, N)`.  No gradients: calls under autograd keep their routes, or take
+        `_context_train_ok`'s families.  `_route` asks twice: `context_rows` (csrc/flow_ctx.hip: one wave per context,
+        up to 16 units; ctx_flow_supported, `_context_rows_slower`) and `wide_context_rows` (csrc/flow_ctx_wide.hip: one
+        workgroup per context, one layer's operand image resident at a time, 17 <= num_units <= 64; ctx_wide_supported,
+        `_context_rows_wide_slower`)."""
         arch, shape, stats_graph, _, plain, _ = facts
-        if not (getattr(self, "context_rows", False) and arch == "coupling" and plain and not stats_graph
+        if not (getattr(self, switch, False) and arch == "coupling" and plain and not stats_graph
                 and z.dim() == 3 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
             return False
-        M = params.size(0)
-        if op != "forward" and shape[0] == 64 and z.size(1) <= 5:
+        mod, supported, slower = _PER_CONTEXT[switch]
+        M, N = params.size(0), z.size(1)
+        if slower(op, shape, N):
             return False
-        return (M > 1 and z.size(0) in ((M,) if op == "forward" else (1, M))
-                and ctxflow_ops.ctx_flow_supported(*shape, z.size(1)))
+        return M > 1 and z.size(0) in ((M,) if op == "forward" else (1, M)) and getattr(mod, supported)(*shape, N)
 
-    def _context_train_ok(self, z, params, facts):
-        """One launch each way for a per-context log_prob under autograd with fewer than 32 samples per context
-        (csrc/flow_ctx.hip forward keeping z0, csrc/flow_ctx_bwd.hip backward): only with the switch `context_training`
-        on (independent of `context_rows`), a coupling stack, float32, grad mode on and params or z requiring grad,
-        constant statistics, a 3-d z, several parameter rows that are the larger batch, one block of z per context --
-        or one shared block that requires no grad: its gradient would need a sum over contexts -- and the fusion setting
-        AUTO or FLOW as for the `padded` family."""
+    def _context_train_ok(self, z, params, facts, switch):
+        """One launch each way for a per-context log_prob under autograd with fewer than 32 samples per context: only
+        with the switch named on (independent of every other switch), a coupling stack, float32, grad mode on and params or
+        z requiring grad, constant statistics, a 3-d z, several parameter rows that are the larger batch, one block of z
+        per context -- or one shared block that requires no grad: its gradient would need a sum over contexts -- the
+        fusion setting AUTO or FLOW as for the `padded` family, and a shape the `*_supported` function of
+        `_PER_CONTEXT[switch]` covers.  `_route` asks twice: `context_training` (csrc/flow_ctx.hip forward keeping z0,
+        csrc/flow_ctx_bwd.hip backward; ctx_train_supported) and `wide_context_training` (csrc/flow_ctx_wide.hip,
+        csrc/flow_ctx_wide_bwd.hip; ctx_wide_train_supported).  No measured exclusion in either."""
         arch, shape, stats_graph, f32, _, _ = facts
-        if not (getattr(self, "context_training", False) and arch == "coupling" and f32 and torch.is_grad_enabled()
+        if not (getattr(self, switch, False) and arch == "coupling" and f32 and torch.is_grad_enabled()
                 and (params.requires_grad or z.requires_grad) and not stats_graph and z.dim() == 3
                 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
             return False
+        mod, supported, _ = _PER_CONTEXT[switch]
         M = params.size(0)
         return (M > 1 and (z.size(0) == M or (z.size(0) == 1 and not z.requires_grad))
-                and ctxtrain_ops.ctx_train_supported(*shape, z.size(1)))
-
-    def _wide_context_rows_ok(self, op, z, params, facts):
-        """`_context_rows_ok` above 16 units (csrc/flow_ctx_wide.hip: one workgroup per context, one layer's operand
-        image resident at a time): only with the switch `wide_context_rows` on, and exactly that predicate's conditions
-        with ctx_wide_supported (17 <= num_units <= 64) in place of ctx_flow_supported.  Its D = 64, N <= 5 exception is a
-        measurement of the 16-unit kernel and is not copied.  One measured exclusion of its own (DESIGN.md 25,
-        profiles/r22_ctxwidebench.txt; M N = 2^16, S = 2, L = 2): ONE sample per context above 48 units, every op, where a
-        workgroup builds every layer's 70 .. 134 KB image for a single row of z and the composition's per-layer kernels
-        stream the same parameters faster (0.89 .. 0.98 x at num_units = 64, D = 4 .. 64; 1.27 .. 1.59 x at N = 8).  The C
-        entries accept the class all the same."""
-        arch, shape, stats_graph, _, plain, _ = facts
-        if not (getattr(self, "wide_context_rows", False) and arch == "coupling" and plain and not stats_graph
-                and z.dim() == 3 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
-            return False
-        M = params.size(0)
-        if z.size(1) == 1 and shape[3] > 48:
-            return False
-        return (M > 1 and z.size(0) in ((M,) if op == "forward" else (1, M))
-                and ctxwide_ops.ctx_wide_supported(*shape, z.size(1)))
-
-    def _wide_context_train_ok(self, z, params, facts):
-        """`_context_train_ok` above 16 units (csrc/flow_ctx_wide.hip forward keeping z0, csrc/flow_ctx_wide_bwd.hip
-        backward): only with the switch `wide_context_training` on (independent of every other switch), and exactly that
-        predicate's conditions with ctx_wide_train_supported in place of ctx_train_supported."""
-        arch, shape, stats_graph, f32, _, _ = facts
-        if not (getattr(self, "wide_context_training", False) and arch == "coupling" and f32 and torch.is_grad_enabled()
-                and (params.requires_grad or z.requires_grad) and not stats_graph and z.dim() == 3
-                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
-            return False
-        M = params.size(0)
-        return (M > 1 and (z.size(0) == M or (z.size(0) == 1 and not z.requires_grad))
-                and ctxwide_ops.ctx_wide_train_supported(*shape, z.size(1)))
+                and getattr(mod, supported)(*shape, z.size(1)))
 
     def _sample_train_ok(self, z, params, facts):
         """One launch forward, one walk kernel backward for frozen-statistics sampling under autograd
@@ -510,32 +538,23 @@ class NormFlow(DensityEstimator):
                 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)
                 and sampletrain_ops.flow_sample_train_supported(z.size(0), params.size(0), z.size(1), *shape))
 
-    def _context_sample_train_ok(self, z, params, facts):
+    def _context_sample_train_ok(self, z, params, facts, switch):
         """One launch each way for frozen-statistics sampling under autograd with several parameter rows and fewer than
-        32 draws per row (csrc/flow_ctx.hip forward, csrc/flow_ctx_sample_bwd.hip backward): only with the switch
-        `context_sample_training` on (independent of `context_rows` and `context_training`), a coupling stack, float32,
-        grad mode on and params requiring grad, constant statistics, a 3-d draw with one block per parameter row, and the
-        fusion setting AUTO or FLOW as for the `padded` family."""
+        32 draws per row: only with the switch named on (independent of every other switch), a coupling stack, float32,
+        grad mode on and params requiring grad, constant statistics, a 3-d draw with one block per parameter row, the
+        fusion setting AUTO or FLOW as for the `padded` family, and a shape the `*_supported` function of
+        `_PER_CONTEXT[switch]` covers.  `_route` asks twice: `context_sample_training` (csrc/flow_ctx.hip forward,
+        csrc/flow_ctx_sample_bwd.hip backward; ctx_sample_supported) and `wide_context_sample_training`
+        (csrc/flow_ctx_wide.hip, csrc/flow_ctx_wide_sample_bwd.hip; ctx_wide_sample_supported).  No measured exclusion in
+        either: the one of `context_rows_wide` (N = 1 above 48 units) is a measurement of another op and is not copied."""
         arch, shape, stats_graph, f32, _, _ = facts
-        if not (getattr(self, "context_sample_training", False) and arch == "coupling" and f32 and torch.is_grad_enabled()
+        if not (getattr(self, switch, False) and arch == "coupling" and f32 and torch.is_grad_enabled()
                 and params.requires_grad and not stats_graph and z.dim() == 3
                 and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
             return False
+        mod, supported, _ = _PER_CONTEXT[switch]
         M = params.size(0)
-        return M > 1 and z.size(0) == M and ctxsample_ops.ctx_sample_supported(*shape, z.size(1))
-
-    def _wide_context_sample_train_ok(self, z, params, facts):
-        """`_context_sample_train_ok` above 16 units (csrc/flow_ctx_wide.hip forward, csrc/flow_ctx_wide_sample_bwd.hip
-        backward): only with the switch `wide_context_sample_training` on (independent of every other switch), and exactly
-        that predicate's conditions with ctx_wide_sample_supported in place of ctx_sample_supported.  The inference
-        exclusion of `_wide_context_rows_ok` (N = 1 above 48 units) is a measurement of another op and is not copied."""
-        arch, shape, stats_graph, f32, _, _ = facts
-        if not (getattr(self, "wide_context_sample_training", False) and arch == "coupling" and f32
-                and torch.is_grad_enabled() and params.requires_grad and not stats_graph and z.dim() == 3
-                and self.fusion in (_lib.FUSE_AUTO, _lib.FUSE_FLOW)):
-            return False
-        M = params.size(0)
-        return M > 1 and z.size(0) == M and ctxwidesample_ops.ctx_wide_sample_supported(*shape, z.size(1))
+        return M > 1 and z.size(0) == M and getattr(mod, supported)(*shape, z.size(1))
 
     def _stats_in_graph(self):
         """Do the cached BatchNorm statistics still carry the graph of the batch-mode forward that produced them
@@ -662,19 +681,23 @@ class NormFlow(DensityEstimator):
             pair = self._train_path(z, params, stats_graph)
             if pair is not None:
                 return Route("train_" + pair, False, False)
-        if op == "log_prob" and self._context_train_ok(z, params, f):
-            return Route("train_context", False, False)
-        if op == "log_prob" and self._wide_context_train_ok(z, params, f):  # 17 .. 64 units: disjoint from the above
-            return Route("train_context_wide", False, False)
-        if op == "forward" and self._sample_train_ok(z, params, f):
-            return Route("train_sample", False, f32_draw)
-        if op == "forward" and self._context_sample_train_ok(z, params, f):
-            return Route("train_context_sample", False, False)
-        if op == "forward" and self._wide_context_sample_train_ok(z, params, f):  # 17 .. 64 units: disjoint from the above
-            return Route("train_context_sample_wide", False, False)
-        if self._context_rows_ok(op, z, params, f):  # asked last: nothing another family takes changes hands
+        # each per-context predicate is asked twice: up to 16 units, then 17 .. 64 (disjoint shape sets, a switch each)
+        if op == "log_prob":
+            if self._context_train_ok(z, params, f, "context_training"):
+                return Route("train_context", False, False)
+            if self._context_train_ok(z, params, f, "wide_context_training"):
+                return Route("train_context_wide", False, False)
+        if op == "forward":
+            if self._sample_train_ok(z, params, f):
+                return Route("train_sample", False, f32_draw)
+            if self._context_sample_train_ok(z, params, f, "context_sample_training"):
+                return Route("train_context_sample", False, False)
+            if self._context_sample_train_ok(z, params, f, "wide_context_sample_training"):
+                return Route("train_context_sample_wide", False, False)
+        # asked last: nothing another family takes changes hands
+        if self._context_rows_ok(op, z, params, f, "context_rows"):
             return Route("context_rows", False, False)
-        if self._wide_context_rows_ok(op, z, params, f):  # 17 .. 64 units: disjoint from the above
+        if self._context_rows_ok(op, z, params, f, "wide_context_rows"):
             return Route("context_rows_wide", False, False)
         return _BIJECTORS
 
@@ -760,18 +783,9 @@ class NormFlow(DensityEstimator):
             elif family == "padded":  # no fused support layer: it runs below as its own kernel
                 z, sld, *written = ops.flow_padded_forward_raw(z, p_dev, *self._flow_args(),
                                                                want_log_q=route.writes_log_q)
-            elif family == "context_rows":  # one wave per context; the support layer as for `padded`
-                z, sld = ctxflow_ops.ctx_flow_forward_raw(z, p_dev, *self._flow_args())
-            elif family == "context_rows_wide":  # one workgroup per context; the support layer as for `padded`
-                z, sld = ctxwide_ops.ctx_wide_forward_raw(z, p_dev, *self._flow_args())
-            elif family == "wide_flow":  # one workgroup per parameter row; the support layer as for `padded`
-                z, sld = wideflow_ops.wide_flow_forward_raw(z, p_dev, *self._flow_args())
-            elif family == "wide_flow_streamed":  # the same with the layers' images streamed through LDS
-                z, sld = widestream_ops.wide_flow_stream_forward_raw(z, p_dev, *self._flow_args())
-            elif family == "train_context_sample":  # one autograd node, one launch each way; the support layer as above
-                z, sld = ctxsample_ops.ctx_flow_sample_train(z, p_dev, *self._flow_args())
-            elif family == "train_context_sample_wide":  # the same above 16 units: one workgroup per context each way
-                z, sld = ctxwidesample_ops.ctx_wide_sample_train(z, p_dev, *self._flow_args())
+            elif family in _SAMPLERS:  # one launch (under autograd: each way); the support layer as for `padded`
+                mod, name = _SAMPLERS[family]
+                z, sld = getattr(mod, name)(z, p_dev, *self._flow_args())
             elif family == "train_sample":  # one autograd node, one backward kernel; the support layer as for `padded`
                 z, sld, *written = sampletrain_ops.flow_sample_train(z, p_dev, *self._flow_args(), self.fusion,
                                                                      want_log_q=route.writes_log_q)
@@ -822,18 +836,9 @@ class NormFlow(DensityEstimator):
         if family == "padded":
             return ops.flow_padded_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
                                                 want_sld=want_sld)
-        if family == "context_rows":
-            return ctxflow_ops.ctx_flow_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
-                                                     want_sld=want_sld)
-        if family == "context_rows_wide":
-            return ctxwide_ops.ctx_wide_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
-                                                     want_sld=want_sld)
-        if family == "wide_flow":
-            return wideflow_ops.wide_flow_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0,
-                                                       want_sld=want_sld)
-        if family == "wide_flow_streamed":
-            return widestream_ops.wide_flow_stream_log_prob_raw(z, params, *self._flow_args(), want_lp=want_lp,
-                                                                want_z0=want_z0, want_sld=want_sld)
+        if family in _DENSITIES:
+            mod, name = _DENSITIES[family]
+            return getattr(mod, name)(z, params, *self._flow_args(), want_lp=want_lp, want_z0=want_z0, want_sld=want_sld)
         return ops.flow_log_prob_raw(z, params, *self._flow_args(), self.fusion, want_lp=want_lp, want_z0=want_z0,
                                      want_sld=want_sld, interval_consts=consts)
 
@@ -883,18 +888,16 @@ class NormFlow(DensityEstimator):
             # support layer first (it is the last bijector of the stack), then the core's density:
             # log q(z) = log q_core(s^-1(z)) - log|det ds| -- same sum as density_estimator.py:395-416
             z, ld_support = self.bijectors[-1].inverse_and_log_det(z)
-        if family in ("ar_fused", "padded", "fused", "context_rows", "context_rows_wide", "wide_flow",
-                      "wide_flow_streamed"):
+        if family in ("ar_fused", "padded", "fused") or family in _DENSITIES:
             log_q = self._fused_density(family, z, params, consts)[0]
         elif family == "ar_train":
             masks, mean, alpha, D, L, U = self._ar_args()
             log_q = ops.ar_flow_log_prob_train(z, params, masks, mean, alpha, consts, D, L, U)
         elif family == "train_padded":  # ... at 2 <= D <= 63 but 32: the reversible pair at the embedded width
             log_q = padtrain_ops.flow_padded_log_prob_train(z, params, *self._flow_args())
-        elif family == "train_context":  # ... per-context rows with fewer than 32 samples each: one launch each way
-            log_q = ctxtrain_ops.ctx_flow_log_prob_train(z, params, *self._flow_args())
-        elif family == "train_context_wide":  # ... the same at 17 <= num_units <= 64
-            log_q = ctxwide_ops.ctx_wide_log_prob_train(z, params, *self._flow_args())
+        elif family in _TRAINERS:  # ... per-context rows with fewer than 32 samples each: one launch each way
+            mod, name = _TRAINERS[family]
+            log_q = getattr(mod, name)(z, params, *self._flow_args())
         elif family != "bijectors":  # training with the BatchNorm statistics constant, one of the two fused pairs
             log_q = ops.flow_log_prob_train(z, params, *self._flow_args(), reversible=family == "train_reversible")
         else:
